@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # or under torchrun (WORLD_SIZE must equal N)
     python bench.py --config ppo [--steps K]                        # secondary: configs[3] phase timing (not the metric)
+    python bench.py --steps K --warmup W --dump-outputs DIR         # + what the last timed step computed, as DIR/<name>.npy
 
 One "step" = one pass of the hot path over one batch: the T=32-step random-policy rollout of
 num_envs=8192 tables (BASELINE.json configs[1]: ONE fused kernel launch writing the full
@@ -17,7 +18,14 @@ runs its own 8192-table shard (weak scaling, no data-path collective — SURVEY 
 macro-steps/s = N * 8192 * 32 * K / max-over-ranks time.  Prints ONE JSON line on rank 0.
 
 Protocol: ranks lined up -> untimed device warm-up (--device-warmup-ms of the same step: steady-state clocks) -> W untimed
-warm-up steps -> barrier + synchronize -> K steps -> synchronize = the rank's time -> barrier -> MAX over ranks.
+warm-up steps -> barrier + synchronize -> K steps -> synchronize = the rank's time -> barrier -> MAX over ranks.  The device
+warm-up runs for a time, not a number of steps: the tables and the draw counter are put back to their initial values after
+it, so that the W + K steps see the same inputs on every run with the same arguments.
+
+`--dump-outputs DIR` (rank 0): after the timed region, what the last timed step computed — the Transition columns, advantages,
+targets, last_obs / last_mask, the terminated count and the post-rollout table state, i.e. what a caller of
+make_random_roll_out_with_gae receives — as float32 / float64 .npy files (see `last_step_outputs`), to compare two builds
+output for output.
 
 `roofline` is measured in THIS run: after the timed region, KERNEL_LAUNCHES back-to-back launches of the rollout kernel
 alone (same rotating buffers, the C-ABI called directly) between ONE pair of HIP events on the launch stream;
@@ -49,6 +57,8 @@ NBUF = int(os.environ.get("BRL_BENCH_NBUF", "3"))  # Transition buffers in rotat
 KERNEL_LAUNCHES = 128      # launches between the one event pair of the kernel-only loop
 METRIC = "env-steps/sec at num_envs=8192, 32-step rollout, 1/2/4/8 MI355X"
 FAKE = os.environ.get("BRL_BENCH_FAKE") == "1"  # launcher self-test (tests/test_bench_launcher.py): gloo, no GPU, no compute
+DUMP_SAMPLE_ENVS = 512     # --dump-outputs: tables whose observation / legal-mask columns are written (fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def synthetic_lut(n: int, seed: int = 0):
@@ -226,6 +236,36 @@ def pmc_traffic():
         return None, None
 
 
+def last_step_outputs(torch, tr, adv, tgt, last_obs, last_mask, tc, packed):
+    """-> {name: float32 / float64 numpy array}: what the step computed, as a caller of make_random_roll_out_with_gae receives
+    it.  The per-row columns [T, n] in full; observation and legal mask for DUMP_SAMPLE_ENVS tables (numpy default_rng(0),
+    sorted; their indices in `sample_envs`); the opaque int64 table state as exact 32-bit halves [n, 16, 2] (low, high)."""
+    n = tr.action.shape[1]
+    cols = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE_ENVS, n), replace=False))
+    idx = torch.as_tensor(cols, device=tr.obs.device)
+    f32 = lambda t: t.float().cpu().numpy()  # noqa: E731  (bool, int32 and float32 values are exact in float32)
+    words = packed.cpu().numpy().view(np.uint32).reshape(packed.shape[0], packed.shape[1], 2)   # little-endian: (low, high)
+    out = {
+        "obs": f32(tr.obs[:, idx]), "legal_action_mask": f32(tr.legal_action_mask[:, idx]),
+        "action": f32(tr.action), "value": f32(tr.value), "reward": f32(tr.reward), "log_prob": f32(tr.log_prob),
+        "done": f32(tr.done), "advantages": f32(adv), "targets": f32(tgt),
+        "last_obs": f32(last_obs[idx]), "last_legal_action_mask": f32(last_mask[idx]),
+        "terminated_count": tc.cpu().numpy().astype(np.float64), "env_state": words.astype(np.float64),
+        "sample_envs": cols.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    return out
+
+
+def write_outputs(dir_, arrays):
+    os.makedirs(dir_, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dir_, name + ".npy"), a)
+    return {"dir": dir_, "bytes": sum(a.nbytes for a in arrays.values()),
+            "arrays": {name: [str(a.dtype), list(a.shape)] for name, a in arrays.items()}}
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # launcher: `python bench.py --gpus N` without torchrun starts the N ranks itself
 # ---------------------------------------------------------------------------------------------------------------
@@ -302,7 +342,7 @@ def gather_ranks(torch, dist, rank, world, dev, local_s, kern_ms, steps, backend
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="rollout", choices=["rollout", "ppo"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -316,7 +356,14 @@ def main():
                     help="untimed: the same step back to back for this long BEFORE the --warmup steps, so that the timed steps see "
                          "the device's steady-state clocks (a launch takes 26.4 us in the first milliseconds after idle, 25.0 us "
                          "from ~50 ms on; 20 timed steps last 0.5 ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64, "
+                         f"< 64 MB: the wide columns for a fixed sample of {DUMP_SAMPLE_ENVS} tables; rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config != "rollout":
+        ap.error("--dump-outputs: the rollout config only")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # before anything initialises a GPU in this process
@@ -403,6 +450,7 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
         env = brl_amd.BridgeBidding(lut=(keys, values), device=dev, env_offset=env_offset)
         state = env.init(0, num_envs=NUM_ENVS)
         packed = state.packed
+        packed0 = packed.clone()   # the initial tables: restored after the device warm-up
         trajs = [alloc_transition(NUM_STEPS, NUM_ENVS, dev) for _ in range(NBUF)]
         # everything a step touches is allocated once: the production loop (brl_amd/train.py) does the same, and at
         # ~30 us of GPU time per step the host must not spend its time in the allocator
@@ -474,6 +522,10 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
                 one_step(ramp_steps + i)
             ramp_steps += 256
             torch.cuda.synchronize()
+    if not FAKE:   # (the warm-up's step count depends on the clock: the steps below start from the initial tables and draw 0)
+        packed.copy_(packed0)
+        tc.zero_()
+        box["draw"] = 0
     for i in range(args.warmup):
         one_step(i)
     barrier()
@@ -483,6 +535,10 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
     if not FAKE:
         torch.cuda.synchronize()
     local = time.perf_counter() - t0  # this rank's K steps, from the common start to its own last store
+    dumped = None
+    if args.dump_outputs and rank == 0 and not FAKE:   # before the kernel-only loop below overwrites the buffers and the tables
+        k = (args.steps - 1) % NBUF
+        dumped = write_outputs(args.dump_outputs, last_step_outputs(torch, trajs[k], advs[k], tgts[k], last_obs, last_mask, tc, packed))
     barrier()
     elapsed = max_over_ranks(local)   # the job's K steps = the slowest rank's (the closing barrier's own latency — one RCCL
                                       # all-reduce, ~0.1 ms, a fifth of 20 steps — is not part of anybody's steps)
@@ -609,6 +665,8 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
                             "fake": "launcher self-test", "none": "single process"}[backend]
     if ranks_error:
         out["ranks_error"] = ranks_error      # (main() exits non-zero)
+    if dumped is not None:
+        out["dump_outputs"] = dict(dumped, step=f"timed step {args.steps} of {args.steps} ({args.warmup} warm-up steps before)")
     if long_run is not None:
         out["long_run"] = long_run
         out["python_api"] = python_api
