@@ -77,20 +77,16 @@ class ActorCritic(nn.Module):
         aw, cw, ab, cb = self.actor.weight, self.critic.weight, self.actor.bias, self.critic.bias
         if cw.device == dev and cb.device == dev and cw.data_ptr() == aw.data_ptr() + 38 * 200 * 4 and cb.data_ptr() == ab.data_ptr() + 38 * 4:
             net.head_w, net.head_b = aw.data_ptr(), ab.data_ptr()       # (FusedFair's flat buffer: the heads are one [39, 200] already)
-        else:   # the two heads as one matrix: a buffer of this module, rewritten when a head parameter has changed (its _version)
+        else:   # the two heads as one matrix: a buffer of this module, rewritten on EVERY call — a version / address key would miss
+            # the writers that bypass autograd's counters (a replayed hipGraph's Adam step leaves every _version as it was)
             if cw.device != dev or cb.device != dev or cw.dtype != torch.float32 or cb.dtype != torch.float32:
                 return None
-            key = (dev, aw._version, cw._version, ab._version, cb._version, aw.data_ptr(), cw.data_ptr(), ab.data_ptr(), cb.data_ptr())
             hw = getattr(self, "_fair_head_w", None)
-            capturing = torch.cuda.is_current_stream_capturing()
             if hw is None or hw.device != dev:
                 hw = self._fair_head_w = torch.empty((39, 200), dtype=torch.float32, device=dev)
                 self._fair_head_b = torch.empty(39, dtype=torch.float32, device=dev)
-                self._fair_head_key = None
             hb = self._fair_head_b
-            if capturing or getattr(self, "_fair_head_key", None) != key:   # (inside a captured graph: re-read per replay)
-                hw[:38].copy_(aw.detach()); hw[38:].copy_(cw.detach()); hb[:38].copy_(ab.detach()); hb[38:].copy_(cb.detach())
-                self._fair_head_key = None if capturing else key
+            hw[:38].copy_(aw.detach()); hw[38:].copy_(cw.detach()); hb[:38].copy_(ab.detach()); hb[38:].copy_(cb.detach())
             net.head_w, net.head_b = hw.data_ptr(), hb.data_ptr()
         logits = torch.empty((n, 38), dtype=torch.float32, device=dev)
         value = torch.empty(n, dtype=torch.float32, device=dev)

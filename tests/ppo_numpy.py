@@ -1,6 +1,6 @@
 """float64 numpy restatement of ONE PPO minibatch step of the reference (src/update.py:86-178 + the optax chain of
-ppo.py:195-211) for the "DeepMind" ReLU MLP (src/models.py:23-33) and the "FAIR" residual net (src/models.py:34-69): forward,
-`_loss_fn`, hand-derived backward, clip_by_global_norm, Adam(eps=1e-5).  TEST INFRASTRUCTURE — the checker for brl_amd/update.py
+ppo.py:195-211) for the "DeepMind" MLPs (src/models.py:23-33, wb5/models.py:34-88) and the "FAIR" residual net (src/models.py:34-69): forward,
+`_loss_fn`, hand-derived backward, clip_by_global_norm, Adam(eps=1e-5) at any step.  TEST INFRASTRUCTURE — the checker for brl_amd/update.py
 and brl_amd/fused_update.py on CPU and GPU."""
 import numpy as np
 
@@ -11,24 +11,47 @@ def params_of(net):
     return [(l.weight.detach().cpu().double().numpy().copy(), l.bias.detach().cpu().double().numpy().copy()) for l in lins]
 
 
-def forward(params, x):
-    hs, zs = [x], []
-    for W, b in params[:-2]:
+def _act(activation):
+    """-> (act, act' as a function of the activation's OUTPUT)"""
+    if activation == "relu":
+        return (lambda z: np.maximum(z, 0.0)), (lambda out: (out > 0).astype(np.float64))
+    return np.tanh, (lambda out: 1.0 - out * out)
+
+
+def forward(params, x, activation="relu", gate_fn=None):
+    """the DeepMind MLP of any depth (src/models.py:23-33, wb5/models.py:34-88) -> (logits, value, hs, zs, dacts): hs[k] = the input of
+    hidden layer k (hs[0] = x), zs[k] its pre-activation, dacts[k] = act'(zs[k]).  gate_fn(k, z, h_in) (ReLU only): the 0/1 gate
+    of layer k instead of z > 0 — a checker of a fp32 step takes the step's own gate where z is within its rounding of 0."""
+    act, dact = _act(activation)
+    hs, zs, dacts = [x], [], []
+    for k, (W, b) in enumerate(params[:-2]):
         z = hs[-1] @ W.T + b
         zs.append(z)
-        hs.append(np.maximum(z, 0.0))
+        if activation == "relu" and gate_fn is not None:
+            gate = np.asarray(gate_fn(k, z, hs[-1]), dtype=bool)
+            h = np.where(gate, z, 0.0)
+            dacts.append(gate.astype(np.float64))
+        else:
+            h = act(z)
+            dacts.append(dact(h))
+        hs.append(h)
     logits = hs[-1] @ params[-2][0].T + params[-2][1]
     value = (hs[-1] @ params[-1][0].T + params[-1][1])[:, 0]
-    return logits, value, hs, zs
+    return logits, value, hs, zs, dacts
 
 
 def head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tgt):
-    """`_loss_fn` on given network outputs (float64) -> (total, (value_loss, loss_actor, entropy, approx_kl, clipfrac),
-    dlogits, dvalue): the derivative w.r.t. the outputs, hand-derived.  cfg["actor_illegal_action_mask"] False = the
-    unmasked policy for the log-prob (src/update.py:18-21); the entropy is always the masked policy's (:132-135)."""
+    """`_loss_fn` on given network outputs (float64) -> (total, (value_loss, loss_actor, entropy, approx_kl, clipfrac, illegal norm / 2),
+    dlogits, dvalue): the derivative w.r.t. the outputs, hand-derived.  cfg["actor_illegal_action_mask"] False = the unmasked policy
+    for the log-prob (src/update.py:18-21); the entropy is always the masked policy's (:132-135); cfg["reward_scaling"]: gae
+    normalised first (src/update.py:31-44, ddof 0); cfg["illegal_action_l2norm_coef"] = c: + c * sigma_1(P * ~mask) / 2 with P the
+    softmax of the UNMASKED logits (src/update.py:136-152), its gradient c / 2 * (u_1 v_1^T * ~mask) pushed back through that
+    softmax (u_1, v_1 from the SVD)."""
     B = logits.shape[0]
     eps = cfg["clip_eps"]
     mask = mask.astype(bool)
+    if cfg.get("reward_scaling", False):
+        gae = (gae - gae.mean()) / (gae.std() + 1e-8)
     masked = cfg.get("actor_illegal_action_mask", True)
     ml = np.where(mask, logits, -np.inf)
     ml = ml - ml.max(1, keepdims=True)
@@ -36,8 +59,9 @@ def head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tg
     p = np.exp(lsm)
     ul = logits - logits.max(1, keepdims=True)
     lsm_u = ul - np.log(np.exp(ul).sum(1, keepdims=True))
+    p_u = np.exp(lsm_u)
     idx = np.arange(B)
-    lsel, psel = (lsm, p) if masked else (lsm_u, np.exp(lsm_u))
+    lsel, psel = (lsm, p) if masked else (lsm_u, p_u)
     lp = lsel[idx, action]
     logratio = lp - old_log_prob
     ratio = np.exp(logratio)
@@ -57,7 +81,6 @@ def head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tg
     plogp = np.where(mask, p * np.where(mask, lsm, 0.0), 0.0)
     ent_i = -plogp.sum(1)
     entropy = ent_i.mean()
-    total = loss_actor + cfg["vf_coef"] * value_loss - cfg["ent_coef"] * entropy
     onehot = np.zeros_like(p)
     onehot[idx, action] = 1.0
     dlogits = dlp[:, None] * (onehot - psel)
@@ -65,76 +88,69 @@ def head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tg
         dlogits = np.where(mask, dlogits, 0.0)
     dH = -np.where(mask, p * (np.where(mask, lsm, 0.0) + ent_i[:, None]), 0.0)
     dlogits = dlogits - cfg["ent_coef"] * dH / B
+    # the illegal-action term: sigma_1 of the illegal probabilities of the unmasked policy (logged whatever its coefficient)
+    u, s, vt = np.linalg.svd(p_u * ~mask, full_matrices=False)
+    illegal = s[0] / 2
+    coef = float(cfg.get("illegal_action_l2norm_coef", 0.0) or 0.0)
+    total = loss_actor + cfg["vf_coef"] * value_loss - cfg["ent_coef"] * entropy + coef * illegal
+    if coef:
+        dP = coef / 2 * np.outer(u[:, 0], vt[0]) * ~mask                  # d sigma_1 / dA = u_1 v_1^T (the sign of the pair cancels)
+        dlogits = dlogits + p_u * (dP - (dP * p_u).sum(1, keepdims=True))  # back through the softmax
     approx_kl = ((ratio - 1) - logratio).mean()
     clipfrac = (np.abs(ratio - 1.0) > eps).mean()
-    return total, (value_loss, loss_actor, entropy, approx_kl, clipfrac), dlogits, dv
+    return total, (value_loss, loss_actor, entropy, approx_kl, clipfrac, illegal), dlogits, dv
 
 
-def loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae, tgt):
-    """-> (total, (value_loss, loss_actor, entropy, approx_kl, clipfrac), grads like params)"""
-    B = obs.shape[0]
-    eps = cfg["clip_eps"]
-    mask = mask.astype(bool)
-    logits, value, hs, zs = forward(params, obs.astype(np.float64))
-    ml = np.where(mask, logits, -np.inf)
-    ml = ml - ml.max(1, keepdims=True)
-    lsm = ml - np.log(np.exp(ml).sum(1, keepdims=True))          # masked log-softmax (src/update.py:12-16)
-    p = np.exp(lsm)
-    idx = np.arange(B)
-    lp = lsm[idx, action]
-    logratio = lp - old_log_prob
-    ratio = np.exp(logratio)
-    # value loss (src/update.py:48-60)
-    vc = old_value + np.clip(value - old_value, -eps, eps)
-    l1, l2 = (value - tgt) ** 2, (vc - tgt) ** 2
-    value_loss = 0.5 * np.maximum(l1, l2).mean()
-    inside_v = np.abs(value - old_value) < eps
-    dv = np.where(l1 >= l2, value - tgt, (vc - tgt) * inside_v) / B * cfg["vf_coef"]
-    # actor loss (src/update.py:116-130)
-    a1, a2 = ratio * gae, np.clip(ratio, 1 - eps, 1 + eps) * gae
-    loss_actor = -np.minimum(a1, a2).mean()
-    inside_r = (ratio > 1 - eps) & (ratio < 1 + eps)
-    dratio = -np.where((a1 < a2) | inside_r, gae, 0.0) / B
-    dlp = dratio * ratio
-    # entropy of the masked policy (src/update.py:132-138), 0 log 0 = 0
-    plogp = np.where(mask, p * np.where(mask, lsm, 0.0), 0.0)
-    ent_i = -plogp.sum(1)
-    entropy = ent_i.mean()
-    total = loss_actor + cfg["vf_coef"] * value_loss - cfg["ent_coef"] * entropy
-    onehot = np.zeros_like(p)
-    onehot[idx, action] = 1.0
-    dlogits = dlp[:, None] * (onehot - p)
-    dH = -np.where(mask, p * (np.where(mask, lsm, 0.0) + ent_i[:, None]), 0.0)   # dH_i / dz_a
-    dlogits += -cfg["ent_coef"] * dH / B
-    dlogits = np.where(mask, dlogits, 0.0)
-    # backward through the MLP
+def loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae, tgt, activation="relu", gate_fn=None):
+    """the DeepMind MLP (any depth, either activation) -> (total, (value_loss, loss_actor, entropy, approx_kl, clipfrac, illegal norm
+    / 2), grads like params): `head_loss` on the forward pass and the backward pass written out."""
+    logits, value, hs, zs, dacts = forward(params, obs.astype(np.float64), activation, gate_fn)
+    total, aux, dlogits, dv = head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tgt)
     grads = [None] * len(params)
     h = hs[-1]
     grads[-2] = (dlogits.T @ h, dlogits.sum(0))
     grads[-1] = (dv[None, :] @ h, np.array([dv.sum()]))
     dh = dlogits @ params[-2][0] + dv[:, None] * params[-1][0]
     for k in range(len(params) - 3, -1, -1):
-        dz = dh * (zs[k] > 0)
+        dz = dh * dacts[k]
         grads[k] = (dz.T @ hs[k], dz.sum(0))
         dh = dz @ params[k][0]
-    approx_kl = ((ratio - 1) - logratio).mean()
-    clipfrac = (np.abs(ratio - 1.0) > eps).mean()
-    return total, (value_loss, loss_actor, entropy, approx_kl, clipfrac), grads
+    return total, aux, grads
+
+
+def global_norm(grads):
+    return float(np.sqrt(sum((gw ** 2).sum() + (gb ** 2).sum() for gw, gb in grads)))
+
+
+def adam_step(cfg, t, params, m, v, grads, lr=None):
+    """step t (1, 2, ...) of clip_by_global_norm(max_grad_norm) + Adam(eps=1e-5) (ppo.py:195-211) with torch's arithmetic
+    (torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6) clamped to 1; torch.optim.Adam: m <- m + (g - m)(1 - b1),
+    v <- b2 v + (1 - b2) g^2, p <- p - lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)).  params / m / v / grads: lists of
+    (W, b) pairs -> (params, m, v, pre-clip global norm)."""
+    lr = cfg["lr"] if lr is None else lr
+    b1, b2, eps = 0.9, 0.999, 1e-5
+    gn = global_norm(grads)
+    scale = min(1.0, cfg["max_grad_norm"] / (gn + 1e-6)) if cfg.get("global_gradient_clipping", True) else 1.0
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    P, M, V = [], [], []
+    for pp, mm, vv, gg in zip(params, m, v, grads):
+        outs = [[], [], []]
+        for x, m_, v_, g in zip(pp, mm, vv, gg):
+            g = g * scale
+            m_ = m_ + (g - m_) * (1.0 - b1)
+            v_ = v_ * b2 + g * g * (1.0 - b2)
+            outs[0].append(x - lr / bc1 * m_ / (np.sqrt(v_) / np.sqrt(bc2) + eps))
+            outs[1].append(m_)
+            outs[2].append(v_)
+        P.append(tuple(outs[0])); M.append(tuple(outs[1])); V.append(tuple(outs[2]))
+    return P, M, V, gn
 
 
 def adam_first_step(cfg, params, grads):
-    """optax.chain(clip_by_global_norm(max_grad_norm), adam(lr, eps=1e-5)) from a fresh state (ppo.py:195-211)."""
-    gn = np.sqrt(sum((gw ** 2).sum() + (gb ** 2).sum() for gw, gb in grads))
-    scale = min(1.0, cfg["max_grad_norm"] / gn) if cfg.get("global_gradient_clipping", True) else 1.0
-    out = []
-    for (W, b), (gw, gb) in zip(params, grads):
-        new = []
-        for x, g in ((W, gw), (b, gb)):
-            g = g * scale
-            m_hat, v_hat = g, g * g            # (1-b1) g / (1-b1) ; (1-b2) g^2 / (1-b2)
-            new.append(x - cfg["lr"] * m_hat / (np.sqrt(v_hat) + 1e-5))
-        out.append(tuple(new))
-    return out, gn
+    """`adam_step` from a fresh state -> (params, pre-clip global norm)"""
+    zeros = [(np.zeros_like(W), np.zeros_like(b)) for W, b in params]
+    P, _, _, gn = adam_step(cfg, 1, params, zeros, zeros, grads)
+    return P, gn
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -148,8 +164,7 @@ def fair_params_of(net):
 def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae, tgt, activation="relu"):
     """-> (total, aux, grads like params): the loss of `head_loss` on the FAIR forward pass and its gradient by reverse-mode
     differentiation of the reference's own statement order (a tape of (kind, ...) entries; no shared code with the build)."""
-    act = (lambda z: np.maximum(z, 0.0)) if activation == "relu" else np.tanh
-    dact = (lambda out: (out > 0).astype(np.float64)) if activation == "relu" else (lambda out: 1.0 - out * out)
+    act, dact = _act(activation)
     x = obs.astype(np.float64)
     inp = x
     tape = []

@@ -2117,6 +2117,17 @@ def test_fused_fair_step_matches_numpy_restatement(activation, rscale, masked, c
     float64 on the CPU): every gradient before the sweep, the losses, the pre-clip norm, every parameter after the first Adam step.
     chain: forward + loss + backward chain as ONE launch (brl_fair_chain, the default) / as ~55 launches (library products +
     brl_mlp_gemm + elementwise kernels)."""
+    _check_fused_fair_step(activation, rscale, masked, chain, 0.0)
+
+
+def test_fused_fair_step_with_illegal_coef_matches_numpy_restatement():
+    """the same with the illegal-action term (src/update.py:136-152: + coef sigma_1(P * ~mask) / 2), which FusedFair runs launch by launch
+    — the step's top singular pair by power iteration on the 38 x 38 Gram matrix (brl_ppo_stats_gram), its gradient brl_ppo_illegal_grad —
+    against the float64 SVD of tests/ppo_numpy.head_loss"""
+    _check_fused_fair_step("relu", False, True, False, 0.5)
+
+
+def _check_fused_fair_step(activation, rscale, masked, chain, ill):
     from brl_amd.models import make_forward_pass
     from brl_amd.roll_out import Transition
     from brl_amd.update import FusedFair, make_update_step
@@ -2124,7 +2135,8 @@ def test_fused_fair_step_matches_numpy_restatement(activation, rscale, masked, c
     from tests.test_update_cpu import CFG, fake_batch
     tb, adv, tgt = fake_batch(4, 256, seed=2)
     B = 1024
-    cfg = dict(CFG, minibatch_size=B, update_epochs=1, lr=1e-3, reward_scaling=rscale, actor_illegal_action_mask=masked, fair_chain=chain)
+    cfg = dict(CFG, minibatch_size=B, update_epochs=1, lr=1e-3, reward_scaling=rscale, actor_illegal_action_mask=masked, fair_chain=chain,
+               illegal_action_l2norm_coef=ill)
     fp = make_forward_pass(activation, "FAIR")
     net = fp.init(4, device="cuda")
     if activation == "tanh":
@@ -2139,9 +2151,7 @@ def test_fused_fair_step_matches_numpy_restatement(activation, rscale, masked, c
                 q.add_(torch.randn(q.shape, device="cuda", generator=gen) * (0.1 if q.dim() == 1 else 0.01))
     P0 = fair_params_of(net)
     flat = Transition(*[x.reshape((B,) + x.shape[2:]) for x in tb])
-    gae64 = adv.reshape(-1).double().numpy()
-    if rscale:                                                  # src/update.py:31-44 (jnp std: ddof = 0)
-        gae64 = (gae64 - gae64.mean()) / (gae64.std() + 1e-8)
+    gae64 = adv.reshape(-1).double().numpy()                    # (head_loss normalises it under reward_scaling: ddof 0)
     want_total, want_aux, G = fair_loss_and_grads(cfg, P0, flat.obs.numpy(), flat.legal_action_mask.numpy(), flat.action.numpy().astype(np.int64),
                                                   flat.value.double().numpy(), flat.log_prob.double().numpy(), gae64,
                                                   tgt.reshape(-1).double().numpy(), activation=activation)
@@ -2149,9 +2159,10 @@ def test_fused_fair_step_matches_numpy_restatement(activation, rscale, masked, c
     rs, (total, aux) = make_update_step(cfg, fp)((net, None, None, None, 0, 9), Transition(*[x.cuda() for x in tb]), adv.cuda(), tgt.cuda())
     fm = rs[1].get("graphed")
     assert isinstance(fm, FusedFair) and fm.chain == chain, rs[1].get("graph_error")
-    assert abs(float(total[0, 0]) - want_total) < 2e-5
+    assert abs(float(total[0, 0]) - want_total) < 2e-5 + ill * 2e-6 * want_aux[5]   # (+ the fp32 Gram's error of sigma_1)
     for k in range(5):
         assert abs(float(aux[k][0, 0]) - want_aux[k]) < 2e-5, k
+    assert abs(float(aux[5][0, 0]) - want_aux[5]) < 1e-4 * want_aux[5]
     assert abs(float(fm.norm[0]) - gn) < 1e-4 * gn
     lins = list(net.l) + [net.actor, net.critic]
     scale = max(np.abs(gw).max() for gw, _ in G)

@@ -1,0 +1,195 @@
+"""The fused PPO minibatch steps against float64, gradient by gradient and Adam step by Adam step.
+
+``FusedMinibatch`` (the default step of the DeepMind MLPs, brl_amd/fused_update.py) writes its backward pass out by hand: the head's
+dW / db ride in extra workgroups of the dz chain, the weight gradients are one grouped bf16x3 launch, the bias gradients are tile sums
+that the clip + Adam launch finishes.  Here every gradient it leaves in its flat buffer, its pre-clip norm, its logged losses and the
+parameters / moments after three successive Adam steps are compared with the float64 restatement tests/ppo_numpy.py (itself checked
+against torch autograd in float64 by tests/test_update_cpu.py), for every switch that changes the code path inside the step.  Also:
+the FAIR network's inference forward (brl_fair_forward) after updates on each update path."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+LR = 1e-3
+
+# one parametrization per line of the step's code paths: (activation, model, minibatch, config overrides)
+CASES = {
+    "relu_defaults": ("relu", "DeepMind", 1024, {}),                       # bf16x3 dW (brl_mlp_gemm_x3_group), own GEMM dz chain
+    "dw_library": ("relu", "DeepMind", 1024, {"dw_gemm": "library"}),     # torch.bmm + torch.mm weight gradients
+    "no_own_gemm": ("relu", "DeepMind", 1024, {"own_gemm": False}),      # torch.mm + brl_act_bwd_colsum[_heads_dw]
+    "own_gemm_fwd": ("relu", "DeepMind", 1024, {"own_gemm_fwd": True}),  # forward layers on brl_mlp_gemm too
+    "tanh_x3": ("tanh", "DeepMind", 1024, {}),
+    "DeepMind_6": ("relu", "DeepMind_6", 1024, {}),
+    "DeepMind_8": ("relu", "DeepMind_8", 1024, {}),                        # 8 weight gradients: a full x3 group
+    "reward_scaling": ("relu", "DeepMind", 1024, {"reward_scaling": True}),
+    "unmasked": ("relu", "DeepMind", 1024, {"actor_illegal_action_mask": False}),
+    "no_value_clipping": ("relu", "DeepMind", 1024, {"value_clipping": False}),
+    "no_global_clipping": ("relu", "DeepMind", 1024, {"global_gradient_clipping": False}),
+    "illegal_coef": ("relu", "DeepMind", 1024, {"illegal_action_l2norm_coef": 0.5}),   # brl_ppo_stats_gram + brl_ppo_illegal_grad
+    "anneal_lr": ("relu", "DeepMind", 1024, {"anneal_lr": True, "num_minibatches": 1, "num_updates": 4}),
+    "B96": ("relu", "DeepMind", 96, {}),       # bf16x3 on, a partial 64-row tile of the bias sums
+    "B100": ("relu", "DeepMind", 100, {}),     # bf16x3 off (B % 32), own GEMM on (B % 4 == 0)
+    "B333": ("relu", "DeepMind", 333, {}),     # both off, odd B
+}
+
+
+def _np(t):
+    return t.detach().cpu().double().numpy()
+
+
+def _ppo_kinks(cfg, logits, value, mask, action, old_value, old_lp, rel=1e-5):
+    """samples whose ratio sits within `rel` of PPO's clip boundaries 1 +- clip_eps, or whose value change sits within `rel` of the
+    value clip: there the derivative jumps, and a fp32 step may fall on the other side than float64"""
+    eps = cfg["clip_eps"]
+    masked = cfg.get("actor_illegal_action_mask", True)
+    lg = np.where(mask, logits, -np.inf) if masked else logits
+    lg = lg - lg.max(1, keepdims=True)
+    lsm = lg - np.log(np.exp(lg).sum(1, keepdims=True))
+    ratio = np.exp(lsm[np.arange(len(action)), action] - old_lp)
+    n_ratio = int((np.minimum(np.abs(ratio - (1 - eps)), np.abs(ratio - (1 + eps))) < rel).sum())
+    n_value = int((np.abs(np.abs(value - old_value) - eps) < rel).sum()) if cfg.get("value_clipping", True) else 0
+    return n_ratio, n_value
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_fused_deepmind_step_matches_float64(case):
+    """Three successive update_step calls, each ONE minibatch step (batch = minibatch, update_epochs = 1), through FusedMinibatch; the
+    float64 reference of step t starts from the GPU's own parameters and moments before it (copied to the host), so errors do not
+    build up.  After each call:
+      * the five logged losses within 2e-5 of float64 (with the illegal-action term the total also carries the fp32 Gram's 2e-6 relative
+        error of sigma_1);
+      * every weight and bias gradient left in the flat buffer (the `.grad` views), the [39, H] head included, within 2e-5 max|g| + 1e-9
+        — the FAIR step's bound; the pre-clip norm (fm.norm) within 1e-4 relative;
+      * parameters and both moments after step t against tests/ppo_numpy.adam_step(t) on the float64 gradients.  Parameters: 0.02 lr_t.
+        A gradient error d moves a parameter by about lr_t d (1 - b1) / (1 - b1^t) / (sqrt(v_hat) + eps); at t = 1 that is lr d / (|g| +
+        eps) (test_update_cpu.check_update_against_numpy's bound); at t = 2, 3 the factor (1 - b1) / (1 - b1^t) is 0.53 / 0.37 and
+        sqrt(v_hat) >= |g_t| sqrt((1 - b2) / (1 - b2^t)) >= |g_t| / sqrt(3) — no more than 0.92 x the first step's sensitivity to the
+        same gradient error, so the first step's bound holds for the later, bias-corrected ones too.  m: (1 - b1) x the gradient's
+        bound, 2e-5 of the largest clipped gradient (biases included); v: (1 - b2) 2 |g| x that bound = 4e-8 of its square, + 1e-6 max|v|
+        (fp32 rounding of v).
+    ReLU gates: where a float64 pre-activation is within 4e-6 of its |h||W| + |b| sum (the fp32 products' rounding) of 0, the gate is the
+    step's own (fm.hs[l] > 0, rows in the step's permuted order); such entries must be fewer than 1e-4 of all.  Samples at PPO's clip
+    kinks (ratio at 1 +- clip_eps, value change at clip_eps, within 1e-5) are counted: at most 2 per step."""
+    from brl_amd.models import make_forward_pass
+    from brl_amd.roll_out import Transition
+    from brl_amd.update import FusedMinibatch, make_optimizer, make_update_step
+    from tests.ppo_numpy import adam_step, forward, loss_and_grads, params_of
+    from tests.test_update_cpu import CFG, fake_batch
+    activation, model, B, over = CASES[case]
+    cfg = dict(CFG, lr=LR, minibatch_size=B, update_epochs=1, graph_update=True, **over)
+    fp = make_forward_pass(activation, model)
+    net = fp.init(4, device="cuda")
+    opt_state = make_optimizer(cfg, net)
+    rs = (net, opt_state, None, None, 0, 9)
+    nl = len(net.body)
+    upd = make_update_step(cfg, fp)
+    for t in (1, 2, 3):
+        tb, adv, tgt = fake_batch(1, B, seed=200 + t)
+        lr_t = LR * (1.0 - (t - 1) / cfg["num_updates"]) if cfg.get("anneal_lr") else LR
+        assert abs(opt_state["opt"].param_groups[0]["lr"] - lr_t) < 1e-12
+        P = params_of(net)
+        lins = list(net.body) + [net.actor, net.critic]
+        st = opt_state["opt"].state
+        M = [tuple(_np(st[q]["exp_avg"]) if q in st else np.zeros(tuple(q.shape)) for q in (l.weight, l.bias)) for l in lins]
+        V = [tuple(_np(st[q]["exp_avg_sq"]) if q in st else np.zeros(tuple(q.shape)) for q in (l.weight, l.bias)) for l in lins]
+        rs, (total, aux) = upd(rs, Transition(*[x.cuda() for x in tb]), adv.cuda(), tgt.cuda())
+        opt_state = rs[1]
+        fm = opt_state.get("graphed")
+        assert isinstance(fm, FusedMinibatch), opt_state.get("graph_error")
+        if case == "B96":
+            assert fm.dw_x3 and fm.own_gemm
+        elif case == "B100":
+            assert not fm.dw_x3 and fm.own_gemm
+        elif case == "B333":
+            assert not fm.dw_x3 and not fm.own_gemm
+        elif case in ("relu_defaults", "tanh_x3", "DeepMind_8"):
+            assert fm.dw_x3 and fm.own_gemm
+        assert fm.own_gemm == (case not in ("no_own_gemm", "B333")) and fm.dw_x3 == (case not in ("dw_library", "B100", "B333"))
+        assert abs(float(fm.lr_dev[0]) - lr_t) < 1e-9
+        assert {int(s_["step"]) for s_ in opt_state["opt"].state.values()} == {t}
+        # the minibatch in the order the step gathered it (its stored activations are in that order)
+        perm = fm.perm[:B].cpu()
+        flat = Transition(*[x.reshape((B,) + x.shape[2:])[perm] for x in tb])
+        args = (flat.obs.numpy(), flat.legal_action_mask.numpy(), flat.action.numpy().astype(np.int64), flat.value.double().numpy(),
+                flat.log_prob.double().numpy(), adv.reshape(-1)[perm].double().numpy(), tgt.reshape(-1)[perm].double().numpy())
+        gate_fn, ambiguous = None, [0]
+        if activation == "relu":
+            hs_gpu = [(fm.hs[l] > 0).cpu().numpy() for l in range(nl)]
+
+            def gate_fn(k, z, h_in, P=P, hs_gpu=hs_gpu):
+                band = 4e-6 * (np.abs(h_in) @ np.abs(P[k][0]).T + np.abs(P[k][1]))
+                amb = np.abs(z) < band
+                gate = z > 0
+                if amb.any():
+                    gate[amb] = hs_gpu[k][amb]
+                    ambiguous[0] += int(amb.sum())
+                return gate
+        logits, value, _, _, _ = forward(P, args[0].astype(np.float64), activation, gate_fn)
+        n_ratio, n_value = _ppo_kinks(cfg, logits, value, args[1].astype(bool), args[2], args[3], args[4])
+        assert n_ratio <= 2 and n_value <= 2, (t, n_ratio, n_value)
+        ambiguous[0] = 0
+        want_total, want_aux, G = loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
+        assert ambiguous[0] <= 1e-4 * B * net.body[0].weight.shape[0] * nl, (t, ambiguous[0])
+        ill = float(cfg.get("illegal_action_l2norm_coef", 0.0))
+        assert abs(float(total[0, 0]) - want_total) < 2e-5 + ill * 2e-6 * want_aux[5], (t, float(total[0, 0]), want_total)
+        for k in range(5):
+            assert abs(float(aux[k][0, 0]) - want_aux[k]) < 2e-5, (t, k, float(aux[k][0, 0]), want_aux[k])
+        assert abs(float(aux[5][0, 0]) - want_aux[5]) < 1e-4 * want_aux[5], (t, float(aux[5][0, 0]), want_aux[5])
+        # every gradient the step left in the flat buffer (the sweep scales them in registers only)
+        gmax = max(np.abs(gw).max() for gw, _ in G)
+        for k, (lin, (gw, gb)) in enumerate(zip(lins, G)):
+            ew = np.abs(_np(lin.weight.grad) - gw).max()
+            eb = np.abs(_np(lin.bias.grad) - gb).max()
+            assert ew < 2e-5 * gmax + 1e-9 and eb < 2e-5 * gmax + 1e-9, (t, k, ew, eb, gmax)
+        P1, M1, V1, gn = adam_step(cfg, t, P, M, V, G, lr=lr_t)
+        assert abs(float(fm.norm[0]) - gn) < 1e-4 * gn, (t, float(fm.norm[0]), gn)
+        clip = min(1.0, cfg["max_grad_norm"] / (gn + 1e-6)) if cfg.get("global_gradient_clipping", True) else 1.0
+        gc = clip * max(max(np.abs(gw).max(), np.abs(gb).max()) for gw, gb in G)    # the largest clipped gradient, biases included
+        vmax = max(np.abs(v_).max() for pair in V1 for v_ in pair)
+        got = params_of(net)
+        worst_p = worst_m = worst_v = moved = 0.0
+        for lin, p1, m1, v1, p0, p_ in zip(lins, P1, M1, V1, P, got):
+            for q, a, mm, vv, a0, b_ in zip((lin.weight, lin.bias), p1, m1, v1, p0, p_):
+                worst_p = max(worst_p, np.abs(b_ - a).max())
+                worst_m = max(worst_m, np.abs(_np(opt_state["opt"].state[q]["exp_avg"]) - mm).max())
+                worst_v = max(worst_v, np.abs(_np(opt_state["opt"].state[q]["exp_avg_sq"]) - vv).max())
+                moved = max(moved, np.abs(a - a0).max())
+        assert worst_p < 0.02 * lr_t and moved > 0.3 * lr_t, (t, worst_p, moved, lr_t, gn)
+        assert worst_m < 2e-5 * gc + 1e-12, (t, worst_m, gc)
+        assert worst_v < 4e-8 * gc * gc + 1e-6 * vmax, (t, worst_v, gc, vmax)
+
+
+@pytest.mark.parametrize("path", ["graphed", "fused", "eager"])
+def test_fair_inference_forward_follows_the_updated_parameters(path):
+    """FAIR's inference forward (`net(x)` under no_grad: brl_fair_forward through ActorCritic._fair_forward) after each of two updates,
+    with a forward between them as a rollout does, against the module's CURRENT parameters in float64 (test_fair_forward_matches_float64's
+    bound).  graphed = the autograd step captured in a hipGraph (GraphedMinibatch): its replayed Adam step writes the parameters without
+    touching their version counters; fused = FusedFair (the heads one block of its flat buffer); eager = the autograd step."""
+    from brl_amd.models import make_forward_pass
+    from brl_amd.roll_out import Transition
+    from brl_amd.update import FusedFair, GraphedMinibatch, make_optimizer, make_update_step
+    from tests.test_update_cpu import CFG, fake_batch
+    fp = make_forward_pass("relu", "FAIR")
+    net = fp.init(3, device="cuda")
+    cfg = dict(CFG, lr=1e-2, minibatch_size=256, update_epochs=1, graph_update=path != "eager", fused_update=path == "fused")
+    rs = (net, make_optimizer(cfg, net), None, None, 0, 5)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = (torch.rand((1000, 480), device="cuda", generator=g) < 0.12).float()
+    upd = make_update_step(cfg, fp)
+    for it in range(2):
+        with torch.no_grad():
+            net(x)                                   # the rollout's forwards between updates
+        tb, adv, tgt = fake_batch(4, 256, seed=60 + it)
+        rs, _ = upd(rs, Transition(*[t_.cuda() for t_ in tb]), adv.cuda(), tgt.cuda())
+        if path != "eager":
+            assert isinstance(rs[1].get("graphed"), FusedFair if path == "fused" else GraphedMinibatch), rs[1].get("graph_error")
+        with torch.no_grad():
+            lg, v = net(x)
+            ref = fp.init(3, device="cpu").double()
+            ref.load_state_dict({k: t_.double().cpu() for k, t_ in net.state_dict().items()})
+            lg64, v64 = ref(x.double().cpu())
+        scale = max(1.0, float(lg64.abs().max()))
+        el, ev = float((lg.double().cpu() - lg64).abs().max()), float((v.double().cpu() - v64).abs().max())
+        assert el < 2e-5 * scale and ev < 2e-5 * scale, (it, el, ev, scale)

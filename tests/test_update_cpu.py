@@ -104,9 +104,13 @@ def test_update_step_shapes_and_progress():
 
 def check_update_against_numpy(device, graph, T=4, N=256, seed=0):
     """One PPO minibatch step (minibatch = the whole batch, one epoch, fresh Adam) of brl_amd.update on `device` vs
-    the float64 numpy restatement tests/ppo_numpy.py: losses, pre-clip gradient norm through the clipped update, and
-    every parameter after the step.  Tolerances: fp32 GEMMs vs fp64 — loss terms 2e-5 absolute; a parameter moves by
-    lr * g / (|g| + 1e-5) on its first Adam step, so 2 % of lr bounds the effect of a 1e-3 relative gradient error."""
+    the float64 numpy restatement tests/ppo_numpy.py: losses, every weight and bias gradient, the pre-clip gradient norm, and
+    every parameter after the step.  Tolerances: fp32 GEMMs vs fp64 — loss terms 2e-5 absolute, gradients 2e-5 of the largest
+    one (the bound of the FAIR step's check); a parameter moves by lr * g / (|g| + 1e-5) on its first Adam step, so 2 % of lr
+    bounds the effect of a 1e-3 relative gradient error.  The gradients left behind: FusedMinibatch keeps the pre-clip ones in its
+    flat buffer (its sweep scales them in registers) and reports the pre-clip norm; the eager path's clip_grad_norm_ scales `.grad`
+    in place by min(1, max_norm / (norm + 1e-6)) — against float64's own factor, which checks the norm."""
+    from brl_amd.update import FusedStep
     from tests.ppo_numpy import adam_first_step, loss_and_grads, params_of
     tb, adv, tgt = fake_batch(T, N, seed=seed)
     B = T * N
@@ -129,6 +133,17 @@ def check_update_against_numpy(device, graph, T=4, N=256, seed=0):
     assert abs(float(total[0, 0]) - want_total) < 2e-5
     for k in range(5):
         assert abs(float(aux[k][0, 0]) - want_aux[k]) < 2e-5, k
+    fused = rs[1].get("graphed")
+    if isinstance(fused, FusedStep):
+        assert abs(float(fused.norm[0]) - gn) < 1e-4 * gn, (float(fused.norm[0]), gn)
+        clip = 1.0
+    else:
+        clip = min(1.0, cfg["max_grad_norm"] / (gn + 1e-6))
+    scale = max(np.abs(gw).max() for gw, _ in G) * clip
+    lins = list(net.body) + [net.actor, net.critic]
+    for k, (lin, (gw, gb)) in enumerate(zip(lins, G)):
+        assert np.abs(lin.weight.grad.detach().cpu().double().numpy() - clip * gw).max() < 2e-5 * scale + 1e-9, ("dW", k)
+        assert np.abs(lin.bias.grad.detach().cpu().double().numpy() - clip * gb).max() < 2e-5 * scale + 1e-9, ("db", k)
     got = params_of(net)
     worst = max(max(np.abs(a - c).max(), np.abs(b - d).max()) for (a, b), (c, d) in zip(got, P1))
     moved = max(np.abs(a - c).max() for (a, _), (c, _) in zip(P0, P1))
@@ -224,3 +239,125 @@ def test_fair_numpy_restatement_matches_autograd_in_float64(activation):
     assert abs(float(total.detach()) - wt) < 1e-12
     for lin, (gw, gb) in zip(list(net.l) + [net.actor, net.critic], G):
         assert np.abs(lin.weight.grad.numpy() - gw).max() < 1e-12 and np.abs(lin.bias.grad.numpy() - gb).max() < 1e-12
+
+
+def _batch64(B, seed):
+    """(flat batch, its float64 copy for ppo_loss, numpy arguments of the restatement) of one B-sample minibatch"""
+    tb, adv, tgt = fake_batch(1, B, seed=seed)
+    flat = Transition(*[x.reshape((B,) + x.shape[2:]) for x in tb])
+    b64 = Transition(flat.done, flat.action, flat.value.double(), flat.reward, flat.log_prob.double(), flat.obs, flat.legal_action_mask)
+    args = (flat.obs.numpy(), flat.legal_action_mask.numpy(), flat.action.numpy().astype(np.int64), flat.value.double().numpy(),
+            flat.log_prob.double().numpy(), adv.reshape(-1).double().numpy(), tgt.reshape(-1).double().numpy())
+    return flat, b64, adv.reshape(-1).double(), tgt.reshape(-1).double(), args
+
+
+def _perturb(net, seed):
+    """hk.Linear's zero biases would hide a bias mix-up: every parameter moved a little"""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for q in net.parameters():
+            q.add_(torch.randn(q.shape, generator=g, dtype=q.dtype) * (0.1 if q.dim() == 1 else 0.01))
+
+
+# the switches of the PPO step (src/update.py): each one changes the loss or its gradient
+SWITCHES = {"defaults": {}, "unmasked": {"actor_illegal_action_mask": False}, "no_value_clipping": {"value_clipping": False},
+            "reward_scaling": {"reward_scaling": True}, "illegal_coef": {"illegal_action_l2norm_coef": 0.5},
+            "all": {"actor_illegal_action_mask": False, "value_clipping": False, "reward_scaling": True, "illegal_action_l2norm_coef": 0.3}}
+
+
+@pytest.mark.parametrize("activation,model,switch", [
+    ("relu", "DeepMind", "defaults"), ("tanh", "DeepMind", "defaults"), ("relu", "DeepMind_6", "defaults"), ("relu", "DeepMind_8", "defaults"),
+    ("relu", "DeepMind", "unmasked"), ("relu", "DeepMind", "no_value_clipping"), ("relu", "DeepMind", "reward_scaling"),
+    ("relu", "DeepMind", "illegal_coef"), ("tanh", "DeepMind", "illegal_coef"), ("tanh", "DeepMind_6", "all")])
+def test_deepmind_numpy_restatement_matches_autograd_in_float64(activation, model, switch):
+    """tests/ppo_numpy.py's DeepMind forward / `head_loss` / backward (the checker of brl_amd.fused_update.FusedMinibatch) against
+    torch autograd through the module and brl_amd.update.ppo_loss, both in float64: the loss, the six logged terms and every
+    gradient to 1e-12, for every activation, depth and switch of the step."""
+    from brl_amd.update import ppo_loss
+    from tests.ppo_numpy import loss_and_grads, params_of
+    cfg = dict(CFG, **SWITCHES[switch])
+    net = make_forward_pass(activation, model).init(3).double()
+    _perturb(net, 5)
+    flat, b64, adv, tgt, args = _batch64(96, seed=2)
+    logits, value = net(flat.obs.double())
+    total, aux = ppo_loss(cfg, logits, value, b64, adv, tgt)
+    total.backward()
+    wt, waux, G = loss_and_grads(cfg, params_of(net), *args, activation=activation)
+    assert abs(float(total.detach()) - wt) < 1e-12
+    for k in range(6):
+        # (clipfrac is a mean of fp32 0/1 flags; without a coefficient the logged norm is the SVD-free estimate)
+        tol = {4: 1e-7, 5: 1e-12 if cfg["illegal_action_l2norm_coef"] else 1e-4 * waux[5]}.get(k, 1e-12)
+        assert abs(float(aux[k]) - waux[k]) < tol, k
+    lins = list(net.body) + [net.actor, net.critic]
+    assert len(G) == len(lins) == (int(model.split("_")[1]) if "_" in model else 4) + 2
+    for k, (lin, (gw, gb)) in enumerate(zip(lins, G)):
+        assert np.abs(lin.weight.grad.numpy() - gw).max() < 1e-12 and np.abs(lin.bias.grad.numpy() - gb).max() < 1e-12, k
+
+
+def test_deepmind_restatement_gate_override():
+    """loss_and_grads' gate_fn (how a checker of a fp32 step takes that step's own ReLU gates): the default gate given back changes
+    nothing; one flipped gate changes that unit's bias gradient"""
+    from tests.ppo_numpy import loss_and_grads, params_of
+    net = make_forward_pass("relu", "DeepMind").init(3).double()
+    _perturb(net, 5)
+    _, _, _, _, args = _batch64(32, seed=4)
+    P = params_of(net)
+    _, _, G0 = loss_and_grads(dict(CFG), P, *args)
+    _, _, G1 = loss_and_grads(dict(CFG), P, *args, gate_fn=lambda k, z, h: z > 0)
+    assert all(np.array_equal(a, c) and np.array_equal(b, d) for (a, b), (c, d) in zip(G0, G1))
+
+    def flip(k, z, h):
+        g = z > 0
+        if k == 2:
+            g[7, 11] = ~g[7, 11]
+        return g
+    _, _, G2 = loss_and_grads(dict(CFG), P, *args, gate_fn=flip)
+    assert abs(G0[2][1][11] - G2[2][1][11]) > 1e-9
+
+
+@pytest.mark.parametrize("activation,switch", [("relu", "illegal_coef"), ("tanh", "all")])
+def test_fair_numpy_restatement_with_switches_matches_autograd_in_float64(activation, switch):
+    """the FAIR checker through `head_loss` with the step's switches (the illegal-action term included) against autograd, float64"""
+    from brl_amd.update import ppo_loss
+    from tests.ppo_numpy import fair_loss_and_grads, fair_params_of
+    cfg = dict(CFG, **SWITCHES[switch])
+    net = make_forward_pass(activation, "FAIR").init(3).double()
+    _perturb(net, 6)
+    flat, b64, adv, tgt, args = _batch64(128, seed=1)
+    logits, value = net(flat.obs.double())
+    total, _ = ppo_loss(cfg, logits, value, b64, adv, tgt)
+    total.backward()
+    wt, _, G = fair_loss_and_grads(cfg, fair_params_of(net), *args, activation=activation)
+    assert abs(float(total.detach()) - wt) < 1e-12
+    for lin, (gw, gb) in zip(list(net.l) + [net.actor, net.critic], G):
+        assert np.abs(lin.weight.grad.numpy() - gw).max() < 1e-12 and np.abs(lin.bias.grad.numpy() - gb).max() < 1e-12
+
+
+@pytest.mark.parametrize("clipping,max_norm", [(True, 0.5), (True, 1e3), (False, 0.5)])
+def test_adam_step_matches_torch_adam_in_float64(clipping, max_norm):
+    """tests/ppo_numpy.adam_step — steps 1, 2 and 3 (bias-corrected, not sign-like after the first) — against
+    torch.nn.utils.clip_grad_norm_ + torch.optim.Adam(eps=1e-5) in float64: parameters and both moments to 1e-15 relative of the
+    parameters' scale; the pre-clip norm to 1e-12 relative.  max_norm 0.5 clips, 1e3 does not."""
+    from tests.ppo_numpy import adam_step
+    cfg = dict(CFG, global_gradient_clipping=clipping, max_grad_norm=max_norm, lr=3e-3)
+    g = torch.Generator().manual_seed(7)
+    shapes = [((16, 8), (16,)), ((3, 16), (3,))]
+    P = [tuple(torch.randn(s, generator=g, dtype=torch.float64) for s in pair) for pair in shapes]
+    tp = [torch.nn.Parameter(x.clone()) for pair in P for x in pair]
+    opt = torch.optim.Adam(tp, lr=cfg["lr"], eps=1e-5)
+    Pn = [tuple(x.numpy().copy() for x in pair) for pair in P]
+    Mn = [tuple(np.zeros_like(x) for x in pair) for pair in Pn]
+    Vn = [tuple(np.zeros_like(x) for x in pair) for pair in Pn]
+    for t in (1, 2, 3):
+        grads = [tuple(torch.randn(x.shape, generator=g, dtype=torch.float64) * (0.3 if t == 2 else 1.0) for x in pair) for pair in P]
+        for q, gr in zip(tp, [x for pair in grads for x in pair]):
+            q.grad = gr.clone()
+        want_norm = float(torch.nn.utils.clip_grad_norm_(tp, max_norm)) if clipping else None
+        opt.step()
+        Pn, Mn, Vn, gn = adam_step(cfg, t, Pn, Mn, Vn, [tuple(x.numpy() for x in pair) for pair in grads])
+        if clipping:
+            assert abs(gn - want_norm) < 1e-12 * want_norm
+        flat = lambda L: np.concatenate([x.reshape(-1) for pair in L for x in pair])   # noqa: E731
+        assert np.abs(flat(Pn) - np.concatenate([q.detach().numpy().reshape(-1) for q in tp])).max() < 1e-15 * 10
+        assert np.abs(flat(Mn) - np.concatenate([opt.state[q]["exp_avg"].numpy().reshape(-1) for q in tp])).max() < 1e-15
+        assert np.abs(flat(Vn) - np.concatenate([opt.state[q]["exp_avg_sq"].numpy().reshape(-1) for q in tp])).max() < 1e-15
