@@ -157,6 +157,7 @@ def lib() -> C.CDLL:
         "brl_mlp_gemm_dh_heads_dw": [i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, i64, _vp, _vp, _vp, i64, i64, i64, i32,
                                      _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
     }
+    sigs.update(sl_signatures())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -172,6 +173,16 @@ EXPORTS = ["brl_last_error", "brl_version", "brl_create", "brl_set_lut", "brl_de
            "brl_eval_step_team", "brl_rollout_random_gae", "brl_ppo_heads_loss_split", "brl_adam_shard_norm", "brl_adam_shard_apply", "brl_ppo_heads_bwd", "brl_ppo_stats_gram",
            "brl_act_bwd_colsum", "brl_act_bwd_colsum_heads_dw", "brl_bias_finalize_ex", "brl_ppo_stats_rows", "brl_mb_gather_bind", "brl_mb_gather_dev", "brl_ppo_illegal_grad", "brl_adam_clip_fin_gather", "brl_mlp_gemm", "brl_mlp_gemm_dh_heads_dw", "brl_mlp_forward_rows",
            "brl_bias_finalize_rows", "brl_fair_chain", "brl_mlp_gemm_group", "brl_fair_forward", "brl_mlp_gemm_x3", "brl_mlp_gemm_x3_workspace", "brl_mlp_gemm_x3_group", "brl_split_planes", "brl_linear_x3p"]
+
+
+def sl_signatures() -> dict:
+    """argtypes of include/brl_sl.h (the supervised pre-trainer's entry points; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32, u64, f32 = C.c_int64, C.c_int, C.c_uint64, C.c_float
+    return {
+        "brl_sl_sample": [i32, _vp, _vp, i64, u64, i64, _vp, _vp, _vp],
+        "brl_sl_replay": [i32, _vp, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp],
+        "brl_sl_loss": [i32, _vp, i64, _vp, _vp, i64, f32, _vp, _vp, _vp, i64, _vp],
+    }
 
 
 def check(rc: int) -> None:

@@ -49,14 +49,16 @@ DEFAULTS = dict(  # ppo.py:122-180 (PPOConfig), same names and defaults
 )
 
 
-def parse_cli(argv):
-    """``key=value`` arguments like the reference's OmegaConf CLI (ppo.py:183)."""
-    cfg = dict(DEFAULTS)
+def parse_cli(argv, defaults=None):
+    """``key=value`` arguments like the reference's OmegaConf CLI (ppo.py:183); ``defaults``: the names, defaults and types
+    (this module's DEFAULTS unless given — brl_amd.sl passes SL_DEFAULTS)."""
+    defaults = DEFAULTS if defaults is None else defaults
+    cfg = dict(defaults)
     for a in argv:
         k, v = a.split("=", 1)
         if k not in cfg:
             raise SystemExit(f"unknown option {k}")
-        d = DEFAULTS[k]
+        d = defaults[k]
         if isinstance(d, bool):
             cfg[k] = v.lower() in ("1", "true")
         elif d is None:
