@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libbrl_hip.so")
 
@@ -188,6 +190,26 @@ def sl_signatures() -> dict:
 def check(rc: int) -> None:
     if rc != 0:
         raise BrlError(f"libbrl_hip error {rc}: {lib().brl_last_error().decode()}")
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def device_index(t) -> int:
+    """the device ordinal of a tensor (the current device for a device without an index)"""
+    i = t.device.index
+    return i if i is not None else torch.cuda.current_device()
+
+
+def stream(index=None) -> int:
+    """the current HIP stream's handle on device ``index`` (default: the current device), what every C-ABI call takes.
+    torch.cuda.current_stream() costs ~9 us per call (device lookups, a Stream object): ~30 us of an evaluator's 75 us host
+    iteration; the raw accessor is the same handle in ~0.3 us."""
+    if index is None:
+        index = torch.cuda.current_device()
+    if _raw_stream is not None:
+        return _raw_stream(index)
+    return torch.cuda.current_stream(index).cuda_stream
 
 
 def ptr(t):

@@ -16,18 +16,9 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, STATE_WORDS, check, ptr
+from ._capi import NUM_ACTIONS, OBS_SIZE, STATE_WORDS, check, ptr, stream
 
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream() -> int:
-    """the current HIP stream's handle (what every C-ABI call takes).  torch.cuda.current_stream() costs ~9 us per call (device
-    lookups, a Stream object): ~30 us of an evaluator's 75 us host iteration; the raw accessor is the same handle in ~0.3 us."""
-    if _raw_stream is not None:
-        return _raw_stream(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
+_stream = stream   # (the name tests and scripts import: the one helper of _capi, not a copy)
 
 
 def load_dds_table(path: str):
@@ -90,7 +81,7 @@ class State:
             t = torch.empty((n,) + shape, dtype=dtype, device=self.packed.device)
             setattr(f, cname, ptr(t))
             new[name] = t
-        check(_capi.lib().brl_get_fields(self.env._h, ptr(self.packed), n, C.byref(f), _stream()))
+        check(_capi.lib().brl_get_fields(self.env._h, ptr(self.packed), n, C.byref(f), stream()))
         self._cache.update(new)
 
     def __getattr__(self, name):
@@ -303,7 +294,7 @@ class BridgeBidding:
             seed = int(k[0].to(torch.int64).sum().item())
         self.seed(seed)
         packed = self._new_packed(num_envs)
-        check(_capi.lib().brl_init_random(self._h, ptr(packed), num_envs, 0, _stream()))
+        check(_capi.lib().brl_init_random(self._h, ptr(packed), num_envs, 0, stream()))
         return State(self, packed)
 
     def init_from_deals(self, hand, dealer, vul_ns, vul_ew, shuffled_players, tricks) -> State:
@@ -323,7 +314,7 @@ class BridgeBidding:
             raise ValueError("shuffled_players rows must be permutations of 0..3")
         packed = self._new_packed(n)
         check(_capi.lib().brl_init_from_deals(self._h, ptr(packed), n, ptr(hand), ptr(dealer), ptr(vul_ns),
-                                              ptr(vul_ew), ptr(sh), ptr(tricks), _stream()))
+                                              ptr(vul_ew), ptr(sh), ptr(tricks), stream()))
         return State(self, packed)
 
     # ---- step ----------------------------------------------------------------------------------
@@ -342,7 +333,7 @@ class BridgeBidding:
         term = torch.empty(n, dtype=torch.bool, device=self.device)
         cur = torch.empty(n, dtype=torch.int32, device=self.device)
         check(_capi.lib().brl_step(self._h, ptr(state.packed), ptr(out), n, ptr(action), int(autoreset), ptr(obs),
-                                   ptr(mask), ptr(rewards), ptr(term), ptr(cur), _stream()))
+                                   ptr(mask), ptr(rewards), ptr(term), ptr(cur), stream()))
         return State(self, out, {"observation": obs, "legal_action_mask": mask, "rewards": rewards,
                                  "terminated": term, "current_player": cur})
 
@@ -354,7 +345,7 @@ class BridgeBidding:
         pid = None
         if player_id is not None:
             pid = torch.as_tensor(player_id, device=self.device).to(torch.int32).expand(n).contiguous()
-        check(_capi.lib().brl_observe(self._h, ptr(packed), n, ptr(pid), ptr(obs), ptr(mask), _stream()))
+        check(_capi.lib().brl_observe(self._h, ptr(packed), n, ptr(pid), ptr(obs), ptr(mask), stream()))
         return obs, mask
 
     def observe(self, state: State, player_id=None):

@@ -7,8 +7,8 @@ from typing import NamedTuple
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr
-from .bridge_bidding import BridgeBidding, State, _stream
+from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr, stream
+from .bridge_bidding import BridgeBidding, State
 
 PASS_ACTION_NUM = 0      # src/duplicate.py:9
 DOUBLE_ACTION_NUM = 1    # src/duplicate.py:10
@@ -35,7 +35,7 @@ class Table_info(NamedTuple):  # src/duplicate.py:138-144
             t = torch.empty((n,) + shape, dtype=dtype, device=dev)
             setattr(f, cname, ptr(t))
             out.append(t)
-        check(_capi.lib().brl_get_fields(state.env._h, ptr(state.packed), n, C.byref(f), _stream()))
+        check(_capi.lib().brl_get_fields(state.env._h, ptr(state.packed), n, C.byref(f), stream()))
         return Table_info(*out)
 
     def _ptrs(self) -> _capi.TableInfoPtrs:
@@ -54,7 +54,7 @@ def _imp_reward(table_a_reward: torch.Tensor, table_b_reward: torch.Tensor, env:
     a = a.to(device=env.device, dtype=torch.float32).reshape(-1, 4).contiguous()
     b = torch.as_tensor(table_b_reward).to(device=env.device, dtype=torch.float32).reshape(-1, 4).contiguous()
     out = torch.empty_like(a)
-    check(_capi.lib().brl_imp_reward(env._h, ptr(a), ptr(b), ptr(out), a.shape[0], _stream()))
+    check(_capi.lib().brl_imp_reward(env._h, ptr(a), ptr(b), ptr(out), a.shape[0], stream()))
     return out[0] if single else out
 
 
@@ -86,7 +86,7 @@ def duplicate_step(step_fn):
         pa, pb = table_a_info._ptrs(), table_b_info._ptrs()
         check(_capi.lib().brl_duplicate_step(env._h, ptr(state.packed), ptr(out), n, ptr(action), C.byref(pa),
                                              C.byref(pb), ptr(obs), ptr(mask), ptr(rewards), ptr(term), ptr(cur),
-                                             _stream()))
+                                             stream()))
         nxt = State(env, out, {"observation": obs, "legal_action_mask": mask, "rewards": rewards,
                                "terminated": term, "current_player": cur})
         return nxt, table_a_info, table_b_info

@@ -20,8 +20,8 @@ import os
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr
-from .bridge_bidding import BridgeBidding, State, _stream
+from ._capi import NUM_ACTIONS, OBS_SIZE, check, device_index, ptr, stream
+from .bridge_bidding import BridgeBidding, State
 from .duplicate import Table_info
 from .models import InferenceSnapshot, make_forward_pass
 from .utils import single_play_step_two_policy_commpetitive_deterministic
@@ -122,9 +122,8 @@ class _Forward:
         need = m * (OBS_SIZE + 2 * hidden)
         if getattr(self, "_scratch", None) is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.float32, device=out.device)
-        di = out.device.index if out.device.index is not None else torch.cuda.current_device()
-        check(_capi.lib().brl_mlp_forward_rows(di, C.byref(self.ref), ptr(obs_bool), ptr(idx), m, ptr(self._scratch),
-                                               self._scratch.numel(), out.data_ptr(), out.stride(0), _stream()))
+        check(_capi.lib().brl_mlp_forward_rows(device_index(out), C.byref(self.ref), ptr(obs_bool), ptr(idx), m, ptr(self._scratch),
+                                               self._scratch.numel(), out.data_ptr(), out.stride(0), stream()))
 
     def __call__(self, obs_bool, obs_f32):
         if self.snap is not None:
@@ -220,9 +219,9 @@ class _DoneWatch:
         live = ptr(self.idx[k]) if self.idx is not None else None
         self.by_word[k] = _HOST_COUNT and _WORD_VISIBLE[0]
         if self.by_word[k]:   # the launch stores tag | count in the pinned word itself (include/brl_hip.h: brl_live_index)
-            check(_capi.lib().brl_live_index(self._h, ptr(terminated), self.n, live, self.host.data_ptr() + 8 * k, self._tag(i), _stream()))
+            check(_capi.lib().brl_live_index(self._h, ptr(terminated), self.n, live, self.host.data_ptr() + 8 * k, self._tag(i), stream()))
             return
-        check(_capi.lib().brl_live_index(self._h, ptr(terminated), self.n, live, ptr(self.dev[k:k + 1]), -1, _stream()))
+        check(_capi.lib().brl_live_index(self._h, ptr(terminated), self.n, live, ptr(self.dev[k:k + 1]), -1, stream()))
         self.host[k:k + 1].copy_(self.dev[k:k + 1], non_blocking=True)
         self.events[k].record()
 
@@ -316,7 +315,7 @@ class _ActiveRows:
         snap = getattr(fwd, "snap", None)
         as_bf16 = snap is not None and snap.planes_for(self.m)      # (brl_linear_x3p: the observation as one bf16 plane)
         x = torch.empty((self.m, OBS_SIZE), dtype=torch.bfloat16 if as_bf16 else torch.float32, device=obs.device)
-        check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(self.idx), self.m, ptr(x), 1 if as_bf16 else 0, _stream()))   # gather + astype
+        check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(self.idx), self.m, ptr(x), 1 if as_bf16 else 0, stream()))   # gather + astype
         out = fwd(None, x)
         self.full[:, :out.shape[1]].index_copy_(0, self.idx, out)   # (rows of finished boards keep their last logits: never used)
         return self.full
@@ -363,7 +362,7 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
                 env._h, ptr(packed), ptr(packed), n, lg.data_ptr(), lg.stride(0), lg.data_ptr(), lg.stride(0),
                 C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
                 C.byref(ps) if ps is not None else None, int(bid_set),
-                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, _stream()))
+                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
             obs = nobs
             if record_actions is not None:
                 record_actions.append(action.clone())
@@ -384,7 +383,7 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
                 env._h, ptr(packed), ptr(packed), n, lg.data_ptr(), lg.stride(0), team,
                 C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
                 C.byref(ps) if ps is not None else None, int(bid_set),
-                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, ptr(obs_f32), _stream()))
+                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, ptr(obs_f32), stream()))
             if record_calls is not None:   # (the calls of THIS loop — -1: the board waited for its team's iteration — for oracle replays)
                 record_calls.append(action.clone())
             obs = nobs
@@ -407,7 +406,7 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
             env._h, ptr(packed), ptr(packed), n, l1.data_ptr(), l1.stride(0), l2.data_ptr(), l2.stride(0),
             C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
             C.byref(ps) if ps is not None else None, int(bid_set),
-            ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, _stream()))
+            ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
         obs = nobs
         if record_actions is not None:
             record_actions.append(action.clone())
@@ -500,7 +499,7 @@ def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, t
             pa = tables[0]._ptrs()
             pb = tables[1]._ptrs() if dup else None
             check(_capi.lib().brl_eval_reduce(eval_env._h, n, C.byref(pa), C.byref(pb) if pb is not None else None,
-                                              ptr(stats.bid_count), ptr(state.packed), ptr(counts), _stream()))
+                                              ptr(stats.bid_count), ptr(state.packed), ptr(counts), stream()))
             c = sh.allsum(counts).to(torch.float64)   # (exact integer counts: the histograms of all ranks' boards)
             fn = float(sh.n_global)
             steps = stats.step_count.to(torch.float32)

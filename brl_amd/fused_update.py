@@ -3,10 +3,13 @@ GEMMs and (under a process group) RCCL collectives.  ``brl_amd.update.make_updat
 the step and its multi-rank forms."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.distributed as dist
 
-from ._capture import quiet_gc
+from ._capi import device_index, stream
+from ._capture import capture, capture_each, preserved, warm_up
 from .roll_out import Transition
 
 
@@ -98,23 +101,23 @@ class FusedStep:
         #             then its one replay (every rank holds a valid graph: the collectives pair up);
         #             other backends: the program once, eagerly
         #   phase 3   the step's graphs                                                                                 -> agree
-        err = None
-        self._saved = None
-        try:
-            self._setup(log_capacity)
-        except Exception as e:
-            err = e
-            self._restore()
-        self._agree(err, "allocation / first launches")
-        self._capture_all()
+        with contextlib.ExitStack() as keep:
+            err = None
+            try:
+                self._setup(log_capacity)
+                # warm-up and capture run real steps on the dummy batch: parameters, moments and counters are put back afterwards
+                keep.enter_context(preserved(tensors=(self.P, self.M, self.V, self.step, self.mb_index)))
+                warm_up(self._run_kernel_groups, 2, no_grad=True)   # (allocator, library heuristics)
+                torch.cuda.synchronize()
+            except Exception as e:
+                err = e
+            self._agree(err, "allocation / first launches")
+            self._capture_all()
 
-    def _restore(self):
-        """the warm-up and the captures run real steps on the dummy batch: parameters, moments and counters as they were"""
-        if self._saved is not None:
-            with torch.no_grad():
-                for t, q in zip((self.P, self.M, self.V, self.step, self.mb_index), self._saved):
-                    t.copy_(q)
-            self._saved = None
+    def _run_kernel_groups(self):
+        for item in self.program:
+            if item[0] == "k":
+                item[1]()
 
     def _setup(self, log_capacity):
         config, params, opt, device, multi = self.cfg, self.params, self.opt, self.dev, self.multi
@@ -200,76 +203,52 @@ class FusedStep:
         self._works = {}
         self.moments_partial = False    # "sharded": True once a step has run and gather_optimizer_state has not
         self.graph = self.graph_multi = self.segs = None
-        # warm-up and capture run real steps on the dummy batch: parameters, moments and counters are put back afterwards
-        self._saved = [t.clone() for t in (self.P, self.M, self.V, self.step, self.mb_index)]
-        self._side = torch.cuda.Stream()
-        self._side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self._side), torch.no_grad():
-            for _ in range(2):      # kernel groups only (allocator, library heuristics)
-                for item in self.program:
-                    if item[0] == "k":
-                        item[1]()
-        torch.cuda.current_stream().wait_stream(self._side)
-        torch.cuda.synchronize()
 
     def _capture_all(self):
-        from ._capture import graph_kwargs
-        config, multi, side = self.cfg, self.multi, self._side
-        gkw = graph_kwargs()
+        config, multi = self.cfg, self.multi
+        err = None
+        scratch = None
         try:
-            err = None
-            scratch = None
-            try:
-                if multi and self.in_graph:
-                    with quiet_gc():
-                        scratch = self._capture_steps(1, gkw)
-                else:
-                    with torch.cuda.stream(side), torch.no_grad():
-                        self._run_program(True)     # (single rank: a third warm-up; gloo: the collectives pair up eagerly)
-                        self._drain()
-                    torch.cuda.current_stream().wait_stream(side)
-            except Exception as e:
-                err = e
-            self._agree(err, "first pass of the program's collectives")
-            if scratch is not None:
-                scratch.replay()
-                torch.cuda.synchronize()
-                del scratch
-            try:
-                with quiet_gc():   # (_capture.py: no collector run while a stream captures)
-                    if self.in_graph:
-                        self.graph = self._capture_steps(1, gkw)
-                        # ... and the same step K times in ONE graph: a replay boundary costs ~5 us (graph launch behind the last
-                        # kernel), the step ~0.23 ms; mb_index lives in device memory, so the K copies walk K minibatches
-                        self.graph_steps = int(config.get("update_graph_steps", 8))
-                        if self.graph_steps > 1:
-                            self.graph_multi = self._capture_steps(self.graph_steps, gkw)
-                    else:
-                        pool = torch.cuda.graph_pool_handle()
-                        self.segs = []          # the program with every run of kernel groups replaced by its graph
-                        run = []
+            if multi and self.in_graph:
+                scratch = capture(lambda: self._program_steps(1), no_grad=True)
+            else:   # (single rank: a third warm-up; gloo: the collectives pair up eagerly)
+                warm_up(lambda: self._program_steps(1), 1, no_grad=True)
+        except Exception as e:
+            err = e
+        self._agree(err, "first pass of the program's collectives")
+        if scratch is not None:
+            scratch.replay()
+            torch.cuda.synchronize()
+            del scratch
+        try:
+            if self.in_graph:
+                # the step once, and the same step K times in ONE graph: a replay boundary costs ~5 us (graph launch behind the last
+                # kernel), the step ~0.23 ms; mb_index lives in device memory, so the K copies walk K minibatches
+                self.graph_steps = int(config.get("update_graph_steps", 8))
+                ks = (1, self.graph_steps) if self.graph_steps > 1 else (1,)
+                graphs = capture_each([lambda k=k: self._program_steps(k) for k in ks], no_grad=True)
+                self.graph, self.graph_multi = graphs[0], (graphs[1] if len(graphs) > 1 else None)
+            else:
+                # the program with every run of kernel groups replaced by its graph (one memory pool)
+                segs = []
+                for item in self.program:
+                    if item[0] == "k":
+                        if segs and segs[-1][0] == "g":
+                            segs[-1][1].append(item[1])
+                        else:
+                            segs.append(("g", [item[1]]))
+                    elif item[0] == "c":
+                        segs.append(item)
 
-                        def close():
-                            if run:
-                                fns = list(run)
-                                g = torch.cuda.CUDAGraph()
-                                with torch.cuda.graph(g, pool=pool, **gkw), torch.no_grad():
-                                    for fn in fns:
-                                        fn()
-                                self.segs.append(("g", g))
-                                run.clear()
-                        for item in self.program:
-                            if item[0] == "k":
-                                run.append(item[1])
-                            elif item[0] == "c":
-                                close()
-                                self.segs.append(item)
-                        close()
-            except Exception as e:
-                err = e
-            self._agree(err, "capture of the step")
-        finally:
-            self._restore()
+                def run(fns):
+                    for fn in fns:
+                        fn()
+                graphs = iter(capture_each([lambda fns=s[1]: run(fns) for s in segs if s[0] == "g"], pool=torch.cuda.graph_pool_handle(),
+                                           no_grad=True))
+                self.segs = [("g", next(graphs)) if s[0] == "g" else s for s in segs]
+        except Exception as e:
+            err = e
+        self._agree(err, "capture of the step")
 
     def _agree(self, err, what):
         """raises on EVERY rank if the phase failed on any (single rank: re-raises its own error)"""
@@ -282,13 +261,10 @@ class FusedStep:
         if not ok:
             raise RuntimeError(f"FusedStep: {what} failed on another rank: no rank builds the fused step")
 
-    def _capture_steps(self, k, gkw):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, **gkw), torch.no_grad():
-            for _ in range(k):
-                self._run_program(True)
-            self._drain()           # every forked stream joins before the capture ends
-        return g
+    def _program_steps(self, k):
+        for _ in range(k):
+            self._run_program(True)
+        self._drain()           # every forked stream joins before the capture ends
 
     def _run_program(self, async_op):
         for item in self.program:
@@ -319,27 +295,26 @@ class FusedStep:
                                                     self.mb_index.data_ptr(), self.mbs, self.x0.data_ptr(), self.mask.data_ptr(),
                                                     self.action.data_ptr(), self.old_v.data_ptr(), self.old_lp.data_ptr(),
                                                     self.adv.data_ptr(), self.tgt.data_ptr(), perm.numel() // self.mbs,
-                                                    self.gargs.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                                                    self.gargs.data_ptr(), stream()))
         if first:
-            self.capi.check(self.lib.brl_mb_gather_dev(self._di(), self.gargs.data_ptr(), self.mbs, torch.cuda.current_stream().cuda_stream))
+            self.capi.check(self.lib.brl_mb_gather_dev(self._di(), self.gargs.data_ptr(), self.mbs, stream()))
 
     def _di(self):
-        return self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        return device_index(self.P)
 
     # ---- clip + Adam on rank slices (multi-rank forms) -----------------------------------------------------------------
     def _shard_norm(self, lo, hi):
         import ctypes as C
         self.capi.check(self.lib.brl_adam_shard_norm(self._di(), self.G.data_ptr(), C.byref(self.geom), lo, hi, 1.0 / self.world,
                                                      self.norm_partials.data_ptr(), self.step.data_ptr(), self.mb_index.data_ptr(),
-                                                     torch.cuda.current_stream().cuda_stream))
+                                                     stream()))
 
     def _shard_apply(self, lo, hi):
         import ctypes as C
         self.capi.check(self.lib.brl_adam_shard_apply(
             self._di(), self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), C.byref(self.geom), lo, hi,
             self.norm_partials.data_ptr(), self.step.data_ptr(), self.lr, self.lr_dev.data_ptr(), float(self.b1), float(self.b2),
-            self.eps, self.max_norm, 1.0 / self.world, self.norm.data_ptr(), self.gargs.data_ptr(), self.mbs,
-            torch.cuda.current_stream().cuda_stream))
+            self.eps, self.max_norm, 1.0 / self.world, self.norm.data_ptr(), self.gargs.data_ptr(), self.mbs, stream()))
 
     # ---- one update_step call -----------------------------------------------------------------------------------
     def begin_update(self, flat: Transition, adv_f, tgt_f, perms):
@@ -425,8 +400,7 @@ class FusedStep:
                 self.opt.state[q]["step"].copy_(self.step)
             self.capi.check(self.lib.brl_ppo_stats_rows(self._di(), self.stat_sums.data_ptr(), self.gram_sums.data_ptr(), self._steps,
                                                         self.mbs, float(self.cfg["vf_coef"]), float(self.cfg["ent_coef"]),
-                                                        self.ill_coef, self.log.data_ptr(),
-                                                        torch.cuda.current_stream().cuda_stream))
+                                                        self.ill_coef, self.log.data_ptr(), stream()))
             self._bind_gather(*self._dummy, first=False)   # (the trajectory may be freed by the caller now)
         self._keep = None
         return self.log[:self._steps]
@@ -643,7 +617,7 @@ class FusedMinibatch(FusedStep):
         if self.own_fwd and l > 0:                            # own kernel: bias + activation in its epilogue
             self.capi.check(self.lib.brl_mlp_gemm(self._di(), 0, 1, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0),
                                                   self.h[l].data_ptr(), self.h[l].stride(0), self.mbs, W.shape[0], W.shape[1], self.act,
-                                                  b.data_ptr(), None, 0, None, None, torch.cuda.current_stream().cuda_stream))
+                                                  b.data_ptr(), None, 0, None, None, stream()))
         elif self.act == 0:                                   # ReLU in the GEMM epilogue
             torch._addmm_activation(b, x, W.t(), use_gelu=False, out=self.h[l])
         else:
@@ -653,7 +627,7 @@ class FusedMinibatch(FusedStep):
         """heads + `_loss_fn` + output gradients (two launches), backward of the merged head down to the top hidden layer's
         pre-activation (one launch)"""
         L, chk, B = self.lib, self.capi.check, self.mbs
-        s = torch.cuda.current_stream().cuda_stream
+        s = stream()
         di, cfg = self._di(), self.cfg
         x = self.h[self.nl - 1]
         chk(L.brl_ppo_heads_loss_split(di, x.data_ptr(), x.stride(0), self.Wh.data_ptr(), self.bh.data_ptr(), self.H,
@@ -686,7 +660,7 @@ class FusedMinibatch(FusedStep):
         """dz_{l-1} = (dz_l W_l) * act'(h_{l-1}) + the tile sums of db_{l-1}; the first of the chain (l = nl - 1) also hosts the head's
         dW_h / db_h partials and the step's statistics sums as extra workgroups"""
         L, chk, B, H = self.lib, self.capi.check, self.mbs, self.H
-        s = torch.cuda.current_stream().cuda_stream
+        s = stream()
         di = self._di()
         first = l == self.nl - 1 and self.dw_deferred
         top = self.h[self.nl - 1]
@@ -715,7 +689,7 @@ class FusedMinibatch(FusedStep):
             dz, GW = self.dzs[l], self.GW[l]
             self.capi.check(self.lib.brl_mlp_gemm(self._di(), 2, 0, dz.data_ptr(), dz.stride(0), src.data_ptr(), src.stride(0),
                                                   GW.data_ptr(), GW.stride(0), GW.shape[0], GW.shape[1], self.mbs, self.act, None, None, 0,
-                                                  None, None, torch.cuda.current_stream().cuda_stream))
+                                                  None, None, stream()))
         else:
             torch.mm(self.dzs[l].t(), src, out=self.GW[l])
 
@@ -726,7 +700,7 @@ class FusedMinibatch(FusedStep):
         for l in range(nl - 1, 0, -1):
             self._dz(l)
         if self.dw_x3:
-            self.capi.check(self.lib.brl_mlp_gemm_x3_group(self._di(), 2, nl, *self._gdw, torch.cuda.current_stream().cuda_stream))
+            self.capi.check(self.lib.brl_mlp_gemm_x3_group(self._di(), 2, nl, *self._gdw, stream()))
             return
         if nl > 1:
             torch.bmm(self.dzs[1:].transpose(1, 2), self.hs[:nl - 1], out=self.GW_hidden)
@@ -734,7 +708,7 @@ class FusedMinibatch(FusedStep):
 
     def _seg_fin(self):
         self.capi.check(self.lib.brl_bias_finalize_ex(self._di(), self._nseg, self._seg_scratch, self._seg_cols, self._seg_tiles,
-                                                      self._seg_db, torch.cuda.current_stream().cuda_stream))
+                                                      self._seg_db, stream()))
 
     def _fin_opt(self):
         """single rank: every sum of partials is finished by extra workgroups of the norm launch (brl_adam_clip_fin_gather)"""
@@ -742,7 +716,7 @@ class FusedMinibatch(FusedStep):
             self._di(), self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.n, self.step.data_ptr(), self.lr,
             self.lr_dev.data_ptr(), float(self.b1), float(self.b2), self.eps, self.max_norm, self.scratch.data_ptr(),
             self.scratch.numel(), self.mb_index.data_ptr(), self.norm.data_ptr(), self.gargs.data_ptr(), self.mbs, self._nseg,
-            self._seg_scratch, self._seg_cols, self._seg_tiles, self._seg_db, torch.cuda.current_stream().cuda_stream))
+            self._seg_scratch, self._seg_cols, self._seg_tiles, self._seg_db, stream()))
 
 
 
@@ -903,7 +877,7 @@ class FusedFair(FusedStep):
         16-row tile = the partials of db_l"""
         dz = self.dz[l]
         self.capi.check(self.lib.brl_act_bwd_colsum(self._di(), dz.data_ptr(), gate.data_ptr(), self.mbs, self.H, dz.stride(0), self.act,
-                                                    self.tiles[l].data_ptr(), torch.cuda.current_stream().cuda_stream))
+                                                    self.tiles[l].data_ptr(), stream()))
 
     def _dx(self, l, gate, out, bias_of=None):
         """out = (dz_l W_l) * act'(gate); bias_of = k: `out` IS dz_k and the launch leaves db_k's partials (brl_mlp_gemm, GATE_COLSUM)"""
@@ -912,8 +886,7 @@ class FusedFair(FusedStep):
             cs = self.tiles[bias_of] if bias_of is not None else None
             self.capi.check(self.lib.brl_mlp_gemm(self._di(), 1, 2, dz.data_ptr(), dz.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(),
                                                   out.stride(0), self.mbs, W.shape[1], W.shape[0], self.act, None, gate.data_ptr(),
-                                                  gate.stride(0), cs.data_ptr() if cs is not None else None, None,
-                                                  torch.cuda.current_stream().cuda_stream))
+                                                  gate.stride(0), cs.data_ptr() if cs is not None else None, None, stream()))
             return
         torch.mm(dz, W, out=out)
         if bias_of is not None:
@@ -927,7 +900,7 @@ class FusedFair(FusedStep):
         """the same through brl_fair_chain: one launch for forward, loss and the backward chain, the weight gradients as four
         products, one launch for every bias gradient and the step's statistics row"""
         cfg, B = self.cfg, self.mbs
-        s = torch.cuda.current_stream().cuda_stream
+        s = stream()
         chk, L, di = self.capi.check, self.lib, self._di()
         chk(L.brl_fair_chain(di, self._net, self.x0.data_ptr(), self.mask.data_ptr(), self.action.data_ptr(), self.old_v.data_ptr(),
                              self.old_lp.data_ptr(), self.adv.data_ptr(), self.tgt.data_ptr(), B, float(cfg["clip_eps"]),
@@ -977,7 +950,7 @@ class FusedFair(FusedStep):
         adv = self.adv
         if cfg.get("reward_scaling", False):                   # src/update.py:31-44 (jnp std: ddof = 0)
             adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
-        s = torch.cuda.current_stream().cuda_stream
+        s = stream()
         chk, L, di = self.capi.check, self.lib, self._di()
         chk(L.brl_ppo_loss(di, self.logits.data_ptr(), 38, self.value.data_ptr(), self.mask.data_ptr(), self.action.data_ptr(),
                            self.old_v.data_ptr(), self.old_lp.data_ptr(), adv.data_ptr(), self.tgt.data_ptr(), B, float(cfg["clip_eps"]),

@@ -4,8 +4,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi
-from ._capi import check, ptr
-from .bridge_bidding import _stream
+from ._capi import check, ptr, stream
 
 
 def gae_scan(env, done, value, reward, last_val, gamma: float, gae_lambda: float):
@@ -21,7 +20,7 @@ def gae_scan(env, done, value, reward, last_val, gamma: float, gae_lambda: float
     # config["gamma"] * config["gae_lambda"] is a Python-float product before it meets an array
     gl = float(torch.tensor(float(gamma) * float(gae_lambda), dtype=torch.float32))
     check(_capi.lib().brl_gae(env._h, ptr(done_u8), ptr(value), ptr(reward), ptr(last_val), float(gamma), gl,
-                              int(T), int(N), ptr(adv), ptr(tgt), _stream()))
+                              int(T), int(N), ptr(adv), ptr(tgt), stream()))
     return adv, tgt
 
 

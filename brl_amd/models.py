@@ -90,9 +90,9 @@ class ActorCritic(nn.Module):
             net.head_w, net.head_b = hw.data_ptr(), hb.data_ptr()
         logits = torch.empty((n, 38), dtype=torch.float32, device=dev)
         value = torch.empty(n, dtype=torch.float32, device=dev)
-        di = dev.index if dev.index is not None else torch.cuda.current_device()
+        di = _capi.device_index(x)
         rc = _capi.lib().brl_fair_forward(di, net, x.data_ptr(), n, 0 if self.act is torch.relu else 1, logits.data_ptr(),
-                                          value.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                                          value.data_ptr(), _capi.stream(di))
         if rc != 0:       # refused (the documented fallback: the layers one by one), never an exception from an optimisation
             return None
         return logits, value
@@ -218,9 +218,8 @@ class InferenceSnapshot:
         from . import _capi
         L = _capi.lib()
         for (w, _), wp in zip(self.lin, self.wp):
-            di = w.device.index if w.device.index is not None else torch.cuda.current_device()
-            _capi.check(L.brl_split_planes(di, w.data_ptr(), w.numel(), wp.data_ptr(), w.numel(),
-                                           torch.cuda.current_stream(w.device).cuda_stream))
+            di = _capi.device_index(w)
+            _capi.check(L.brl_split_planes(di, w.data_ptr(), w.numel(), wp.data_ptr(), w.numel(), _capi.stream(di)))
 
     def planes_for(self, n):
         """True where a forward of `n` rows runs on brl_linear_x3p: its input may then come as bf16 (the 0/1 observation is exact in it)"""
@@ -231,8 +230,8 @@ class InferenceSnapshot:
         brl_mlp_gemm_x3: splitting it first costs what the first layer then saves); every layer writes the planes of its output, the last
         one fp32 (what the heads' product reads)"""
         from . import _capi
-        L, st = _capi.lib(), torch.cuda.current_stream(x.device).cuda_stream
-        di = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        di = _capi.device_index(x)
+        L, st = _capi.lib(), _capi.stream(di)
         n, k = x.shape
         xp, npx, sx = x, 1, 0
         y = None
@@ -286,10 +285,9 @@ class InferenceSnapshot:
         if self.env is not None and self.own_cast and obs.dtype in (torch.bool, torch.uint8) and obs.is_cuda and obs.is_contiguous() \
                 and self.dtype in self._FMT:
             from . import _capi
-            from .bridge_bidding import _stream
             dt = torch.bfloat16 if (self.dtype == torch.float32 and obs.dim() == 2 and self.planes_for(obs.shape[0])) else self.dtype
             x = torch.empty(obs.shape, dtype=dt, device=obs.device)
-            _capi.check(_capi.lib().brl_obs_cast(self.env._h, obs.data_ptr(), obs.numel() // 480, x.data_ptr(), self._FMT[dt], _stream()))
+            _capi.check(_capi.lib().brl_obs_cast(self.env._h, obs.data_ptr(), obs.numel() // 480, x.data_ptr(), self._FMT[dt], _capi.stream()))
             return x
         if self.dtype == torch.float32 and obs.dim() == 2 and self.planes_for(obs.shape[0]):
             if obs.dtype in (torch.bool, torch.uint8):
@@ -302,8 +300,7 @@ class InferenceSnapshot:
         """the hidden layers: x [n, 480] in ``self.dtype`` -> [n, hidden]"""
         if self.body_nk is not None and x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] > 0:
             from . import _capi
-            from .bridge_bidding import _stream
-            L, fmt, st = _capi.lib(), self._FMT[self.dtype], _stream()
+            L, fmt, st = _capi.lib(), self._FMT[self.dtype], _capi.stream()
             for w, b in self.body_nk:
                 y = torch.empty((x.shape[0], w.shape[0]), dtype=self.dtype, device=x.device)
                 _capi.check(L.brl_linear_act(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(),
@@ -318,8 +315,8 @@ class InferenceSnapshot:
                                "planes path only: >= 4096 contiguous rows)")
         if self.gemm_x3 and x.is_cuda and x.dim() == 2 and x.shape[0] >= 4096 and x.is_contiguous() and x.data_ptr() % 16 == 0:
             from . import _capi
-            L, st = _capi.lib(), torch.cuda.current_stream(x.device).cuda_stream
-            di = x.device.index if x.device.index is not None else torch.cuda.current_device()
+            di = _capi.device_index(x)
+            L, st = _capi.lib(), _capi.stream(di)
             for w, b in self.lin:      # nn.Linear's own layout: y = relu(x W^T + b), W [out, in]
                 y = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
                 _capi.check(L.brl_mlp_gemm_x3(di, 0, 1, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
@@ -349,8 +346,7 @@ class InferenceSnapshot:
         if not (x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] > 0):
             return None
         from . import _capi
-        from .bridge_bidding import _stream
-        L, fmt, st, n = _capi.lib(), self._FMT[self.dtype], _stream(), x.shape[0]
+        L, fmt, st, n = _capi.lib(), self._FMT[self.dtype], _capi.stream(), x.shape[0]
         for w, b in self.body_nk[:-1]:
             y = torch.empty((n, w.shape[0]), dtype=self.dtype, device=x.device)
             _capi.check(L.brl_linear_act(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(),

@@ -15,8 +15,9 @@ from typing import NamedTuple
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr
-from .bridge_bidding import BridgeBidding, State, _stream
+from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr, stream
+from ._capture import capture_each, warm_up
+from .bridge_bidding import BridgeBidding, State
 from .models import InferenceSnapshot
 from .utils import MODE, SAMPLE, UNMASKED, _pass_logits, policy_step
 
@@ -65,7 +66,7 @@ def make_random_roll_out(config, env: BridgeBidding):
         last_obs = torch.empty((n, OBS_SIZE), dtype=torch.bool, device=env.device) if want_last else None
         last_mask = torch.empty((n, NUM_ACTIONS), dtype=torch.bool, device=env.device) if want_last else None
         check(_capi.lib().brl_rollout_random(env._h, ptr(env_state.packed), n, T, substeps, int(rng) & 0xFFFFFFFF,
-                                             reward_scale, C.byref(p), ptr(last_obs), ptr(last_mask), ptr(tc), _stream()))
+                                             reward_scale, C.byref(p), ptr(last_obs), ptr(last_mask), ptr(tc), stream()))
         cache = {"observation": last_obs, "legal_action_mask": last_mask} if want_last else None
         new_state = State(env, env_state.packed, cache)  # updated in place; last_obs written by the same launch
         return (params, opt_state, new_state, last_obs, tc, int(rng) + T * substeps), traj
@@ -108,7 +109,7 @@ def make_random_roll_out_with_gae(config, env: BridgeBidding):
         tgt = out_tgt if out_tgt is not None else torch.empty_like(adv)
         check(_capi.lib().brl_rollout_random_gae(env._h, ptr(env_state.packed), n, T, int(rng) & 0xFFFFFFFF, reward_scale,
                                                  C.byref(p), ptr(last_obs), ptr(last_mask), ptr(tc), ptr(lv), gamma, gl,
-                                                 ptr(adv), ptr(tgt), _stream()))
+                                                 ptr(adv), ptr(tgt), stream()))
         new_state = State(env, env_state.packed, {"observation": last_obs, "legal_action_mask": last_mask})
         return (params, opt_state, new_state, last_obs, tc, int(rng) + T), traj, adv, tgt
 
@@ -280,26 +281,17 @@ class _PolicyRollout:
                         obs=obs_out if fin else None, mask=mask_out if fin else None, rewards_acc=racc,
                         terminated_acc=tacc, current_player=cur[(t + 1) & 1] if fin else None, draw_base=self.draw, ext=ext)
 
+    def _macro_steps(self, ts):
+        for t in ts:
+            self._macro_step(t)
+
     def _capture(self):
-        # warm-up on a side stream (allocator, hipBLASLt heuristics), then one capture per scan step
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for t in range(min(self.T, 2)):
-                self._macro_step(t)
-        torch.cuda.current_stream().wait_stream(side)
-        pool = torch.cuda.graph_pool_handle()
-        graphs = []
-        from ._capture import graph_kwargs, quiet_gc
-        gkw = graph_kwargs()   # (thread-local error mode only beside an RCCL watchdog thread: _capture.py)
-        with torch.no_grad(), quiet_gc():   # (a graph freed by the collector mid-capture would abort the process: _capture.py)
-            for t0 in range(0, self.T, self.graph_steps):   # (a replay boundary costs ~8 us of idle GPU: several scan steps per graph)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, **gkw):
-                    for t in range(t0, min(t0 + self.graph_steps, self.T)):
-                        self._macro_step(t)
-                graphs.append(g)
-        self.graphs = graphs
+        # warm-up on a side stream (allocator, hipBLASLt heuristics), then graph_steps scan steps per graph, one memory pool
+        # (a replay boundary costs ~8 us of idle GPU: several scan steps per graph)
+        warm_up(lambda: self._macro_steps(range(min(self.T, 2))), 1, no_grad=True)
+        spans = [range(t0, min(t0 + self.graph_steps, self.T)) for t0 in range(0, self.T, self.graph_steps)]
+        self.graphs = capture_each([lambda ts=ts: self._macro_steps(ts) for ts in spans], pool=torch.cuda.graph_pool_handle(),
+                                   no_grad=True)
 
     def _load(self, env_state, last_obs, terminated_count, rng):
         traj = self.traj

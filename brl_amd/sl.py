@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from . import _capi, checkpoint
+from ._capi import device_index, stream
+from ._capture import capture_each, preserved, warm_up
 from .models import make_forward_pass
 from .sl_data import CALL_NAMES, TrajectorySet, decision_points, hand_string, load_trajectories
 
@@ -36,14 +38,6 @@ MISSING_DATA_HINT = ("Please generate your own supervised training data or downl
 TOP_K_ACTIONS = 5
 
 
-def _dev_index(t: torch.Tensor) -> int:
-    return t.device.index if t.device.index is not None else torch.cuda.current_device()
-
-
-def _stream(t: torch.Tensor):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 class DeviceSet:
     """a TrajectorySet on the GPU (hands as int64: the same 64 bits)"""
 
@@ -57,22 +51,24 @@ class DeviceSet:
 
 # ---- the three entry points ---------------------------------------------------------------------------------------------------
 def sl_sample(data: DeviceSet, counter: torch.Tensor, seed: int, traj: torch.Tensor, pos: torch.Tensor) -> None:
-    _capi.check(_capi.lib().brl_sl_sample(_dev_index(traj), counter.data_ptr(), data.offsets.data_ptr(), data.n,
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, traj.shape[0], traj.data_ptr(), pos.data_ptr(),
-                                           _stream(traj)))
+    di = device_index(traj)
+    _capi.check(_capi.lib().brl_sl_sample(di, counter.data_ptr(), data.offsets.data_ptr(), data.n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           traj.shape[0], traj.data_ptr(), pos.data_ptr(), stream(di)))
 
 
 def sl_replay(data: DeviceSet, traj, pos, obs, mask, label) -> None:
-    _capi.check(_capi.lib().brl_sl_replay(_dev_index(obs), data.hands.data_ptr(), data.offsets.data_ptr(), data.calls.data_ptr(),
-                                           data.n, _capi.ptr(traj), _capi.ptr(pos), traj.shape[0], _capi.ptr(obs), _capi.ptr(mask),
-                                           _capi.ptr(label), _stream(obs)))
+    di = device_index(obs)
+    _capi.check(_capi.lib().brl_sl_replay(di, data.hands.data_ptr(), data.offsets.data_ptr(), data.calls.data_ptr(), data.n,
+                                           _capi.ptr(traj), _capi.ptr(pos), traj.shape[0], _capi.ptr(obs), _capi.ptr(mask),
+                                           _capi.ptr(label), stream(di)))
 
 
 def sl_loss(logits, label, mask, ent_coef: float, dlogits, out, counter=None, advance: int = 0) -> None:
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
-    _capi.check(_capi.lib().brl_sl_loss(_dev_index(logits), logits.data_ptr(), logits.stride(0), _capi.ptr(label), _capi.ptr(mask),
-                                         label.shape[0], float(ent_coef), _capi.ptr(dlogits), out.data_ptr(),
-                                         None if counter is None else counter.data_ptr(), int(advance), _stream(logits)))
+    di = device_index(logits)
+    _capi.check(_capi.lib().brl_sl_loss(di, logits.data_ptr(), logits.stride(0), _capi.ptr(label), _capi.ptr(mask), label.shape[0],
+                                         float(ent_coef), _capi.ptr(dlogits), out.data_ptr(),
+                                         None if counter is None else counter.data_ptr(), int(advance), stream(di)))
 
 
 def make_optimizer(net: torch.nn.Module, learning_rate: float):
@@ -123,43 +119,16 @@ class SLStep:
             logits2, _ = self.net(b.obs)
         sl_loss(logits2, b.label, b.mask, self.ent, None, self.post[s], self.counter, self.B)
 
+    def _steps(self, k: int):
+        for s in range(k):
+            self._step(s)
+
     def _capture(self):
-        # Warm-up and capture run the real step: snapshot parameters, optimizer state and the stream counter and put them back
-        # in place afterwards, also when capture fails (the graphs hold these tensors' addresses) — as update.GraphedMinibatch.
-        from ._capture import quiet_gc
-        params = list(self.net.parameters())
-        saved_p = [p.detach().clone() for p in params]
-        saved_s = {p: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
-                   for p, st in self.opt.state.items()}
-        saved_c = self.counter.clone()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    self._step(0)
-            torch.cuda.current_stream().wait_stream(side)
-            for k in sorted({1, self.S}):
-                g = torch.cuda.CUDAGraph()
-                with quiet_gc(), torch.cuda.graph(g):
-                    for s in range(k):
-                        self._step(s)
-                self.graphs[k] = g
-        finally:
-            with torch.no_grad():
-                for p, q in zip(params, saved_p):
-                    p.copy_(q)
-                for p, st in self.opt.state.items():
-                    old = saved_s.get(p)
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            if old is not None and k in old:
-                                v.copy_(old[k])
-                            else:
-                                v.zero_()   # state created by the warm-up: zero moments / step 0 == a fresh Adam state
-                        elif old is not None and k in old:
-                            st[k] = old[k]
-                self.counter.copy_(saved_c)
+        # warm-up and capture run the real step: parameters, optimizer state and the stream counter are put back afterwards
+        ks = sorted({1, self.S})
+        with preserved(self.net.parameters(), self.opt, tensors=(self.counter,)):
+            warm_up(lambda: self._step(0), 3)
+            self.graphs = dict(zip(ks, capture_each([lambda k=k: self._steps(k) for k in ks])))
 
     def run(self, k: int):
         """k <= S steps: one S-step replay when k == S, else k 1-step replays.  Returns the device metrics rows [k, 4] (total,

@@ -19,7 +19,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ._capture import quiet_gc
+from ._capture import capture, preserved, warm_up
 from .fused_update import FusedFair, FusedMinibatch, FusedStep   # noqa: F401  (the default paths of update_step; re-exported)
 from .roll_out import Transition
 
@@ -128,7 +128,7 @@ def ppo_loss_fused(config, logits, value, batch: Transition, gae, targets):
     partials = torch.empty(((B + 3) // 4, 8), dtype=torch.float32, device=dev)
     illp = torch.empty((B, 38), dtype=torch.float32, device=dev)
     out = torch.empty(8, dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = _capi.stream()
     L = _capi.lib()
     old_v, old_lp, gae_c, tgt_c = f32(batch.value), f32(batch.log_prob), f32(gae), f32(targets)
     _capi.check(L.brl_ppo_loss(dev.index, logits_c.data_ptr(), logits_c.stride(0), value_c.data_ptr(), mask.data_ptr(),
@@ -184,38 +184,11 @@ class GraphedMinibatch:
                              z((mbs, 38), torch.bool))
         self.mb.legal_action_mask[:, 0] = True  # a valid dummy batch for the warm-up iterations
         self.gae, self.tgt = z((mbs,), torch.float32), z((mbs,), torch.float32)
-        # Warm-up and capture run the REAL optimizer on a dummy batch: snapshot the parameters and the optimizer state
-        # (moments, step counts — the graph may be built after eager steps or from a loaded optimizer) and put them
-        # back IN PLACE afterwards, also when capture fails (the captured graph holds these tensors' addresses).
-        saved_p = [p.detach().clone() for p in params.parameters()]
-        saved_s = {p: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
-                   for p, st in opt.state.items()}
-        self.graph = None
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    self._step()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with quiet_gc(), torch.cuda.graph(graph):   # (_capture.py: no collector run while a stream captures)
-                self.out = self._step()
-            self.graph = graph
-        finally:
-            with torch.no_grad():
-                for p, q in zip(params.parameters(), saved_p):
-                    p.copy_(q)
-                for p, st in opt.state.items():
-                    old = saved_s.get(p)
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            if old is not None and k in old:
-                                v.copy_(old[k])
-                            else:
-                                v.zero_()  # state created by the warm-up: zero moments / step 0 == a fresh Adam state
-                        elif old is not None and k in old:
-                            st[k] = old[k]
+        # Warm-up and capture run the REAL optimizer on a dummy batch: the parameters and the optimizer state (moments, step
+        # counts — the graph may be built after eager steps or from a loaded optimizer) are put back afterwards.
+        with preserved(params.parameters(), opt):
+            warm_up(self._step, 3)
+            self.graph = capture(self._capture_step)
 
     def _step(self):
         logits, value = self.fp.apply(self.params, self.mb.obs.to(torch.float32))
@@ -225,6 +198,9 @@ class GraphedMinibatch:
             torch.nn.utils.clip_grad_norm_(self.params.parameters(), self.cfg["max_grad_norm"])
         self.opt.step()
         return total, torch.stack(aux)
+
+    def _capture_step(self):
+        self.out = self._step()
 
     def run(self, mb: Transition, gae, tgt):
         for name in ("action", "value", "log_prob", "obs", "legal_action_mask"):  # what _loss_fn reads (not done / reward)

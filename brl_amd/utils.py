@@ -9,8 +9,8 @@ from __future__ import annotations
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr
-from .bridge_bidding import BridgeBidding, State, _stream
+from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr, stream
+from .bridge_bidding import BridgeBidding, State
 
 SAMPLE, MODE = 0, 1  # pi.sample(seed) / pi.mode()
 UNMASKED = 2         # OR-ed in: the categorical ranges over all 38 actions (src/roll_out.py:33-39)
@@ -63,7 +63,7 @@ def policy_step(env: BridgeBidding, packed_in, packed_out, logits, mode: int, dr
         check(_capi.lib().brl_policy_step_ex(env._h, ptr(packed_in), ptr(packed_out), n, None, NUM_ACTIONS, int(mode), ptr(draw_base),
                                              int(draw) & 0xFFFFFFFF, int(bool(autoreset)), ptr(action), ptr(log_prob), ptr(obs),
                                              ptr(mask), ptr(rewards_acc), ptr(terminated_acc), ptr(current_player), C.byref(ext),
-                                             _stream()))
+                                             stream()))
         return
     if ext is None or not ext.in_fmt:
         logits = logits.to(torch.float32)
@@ -77,18 +77,18 @@ def policy_step(env: BridgeBidding, packed_in, packed_out, logits, mode: int, dr
                                              logits.stride(0), int(mode), ptr(draw_base), int(draw) & 0xFFFFFFFF,
                                              int(bool(autoreset)), ptr(action), ptr(log_prob), ptr(obs), ptr(mask),
                                              ptr(rewards_acc), ptr(terminated_acc), ptr(current_player), C.byref(ext),
-                                             _stream()))
+                                             stream()))
         return
     if draw_base is not None or logits.stride(0) != NUM_ACTIONS:
         check(_capi.lib().brl_policy_step_at(env._h, ptr(packed_in), ptr(packed_out), n, logits.data_ptr(),
                                              logits.stride(0), int(mode), ptr(draw_base), int(draw) & 0xFFFFFFFF,
                                              int(bool(autoreset)), ptr(action), ptr(log_prob), ptr(obs), ptr(mask),
-                                             ptr(rewards_acc), ptr(terminated_acc), ptr(current_player), _stream()))
+                                             ptr(rewards_acc), ptr(terminated_acc), ptr(current_player), stream()))
         return
     check(_capi.lib().brl_policy_step(env._h, ptr(packed_in), ptr(packed_out), n, ptr(logits), int(mode),
                                       int(draw) & 0xFFFFFFFF, int(bool(autoreset)), ptr(action), ptr(log_prob),
                                       ptr(obs), ptr(mask), ptr(rewards_acc), ptr(terminated_acc),
-                                      ptr(current_player), _stream()))
+                                      ptr(current_player), stream()))
 
 
 _PASS_LOGITS = {}
