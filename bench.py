@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]           # N > 1: starts N ranks itself (one per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # or under torchrun (WORLD_SIZE must equal N)
+    python bench.py --full [--steps K] [--warmup W]                 # + roofline, long_run, python_api, cpu_baseline, secondary
     python bench.py --config ppo [--steps K]                        # secondary: configs[3] phase timing (not the metric)
     python bench.py --steps K --warmup W --dump-outputs DIR         # + what the last timed step computed, as DIR/<name>.npy
 
@@ -27,9 +28,16 @@ targets, last_obs / last_mask, the terminated count and the post-rollout table s
 make_random_roll_out_with_gae receives — as float32 / float64 .npy files (see `last_step_outputs`), to compare two builds
 output for output.
 
-`roofline` is measured in THIS run: after the timed region, KERNEL_LAUNCHES back-to-back launches of the rollout kernel
+A plain run does what the headline figure needs and nothing else: set-up, the warm-ups, the K timed steps, the dump if asked
+for, the line (`roofline` and `cpu_baseline` are null in it, `full` is false).  Everything else the benchmark measures is
+behind `--full`, after the timed region and the dump, in the same process:
+
+`roofline` (--full) is measured in THIS run: after the timed region, KERNEL_LAUNCHES back-to-back launches of the rollout kernel
 alone (same rotating buffers, the C-ABI called directly) between ONE pair of HIP events on the launch stream;
 `roofline.plain_fill`: a plain fill of the bytes one launch writes, timed the same way (the box's store ceiling).
+`long_run` / `python_api` (--full, N = 1): the same step 2000 times, and through the public Python surface.  `cpu_baseline`
+(--full, N = 1): the CPU oracle on this box's host cores.  `secondary` (--full, N = 1): configs[2] / configs[3] with the policy
+in the loop.  `--no-cpu-baseline` / `--no-secondary` take single legs out of a `--full` run.
 """
 from __future__ import annotations
 
@@ -345,10 +353,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="rollout", choices=["rollout", "ppo"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and the dump), also measure everything else: `roofline` (the rollout kernel alone, "
+                         "a plain fill), `long_run` and `python_api`, `cpu_baseline` and `secondary` (the last four at N=1 only); "
+                         "off by default: a plain run times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip `secondary` (configs[2] duplicate evaluation and configs[3] ppo.py phases with the MLP in the "
-                         "loop, ~30 s, N=1 only) and `long_run`")
+                    help="with --full: skip `secondary` (configs[2] duplicate evaluation and configs[3] ppo.py phases with the MLP in "
+                         "the loop, ~30 s, N=1 only), `long_run` and `python_api`")
     ap.add_argument("--secondary-budget-s", type=float, default=60.0,
                     help="time budget of the `secondary` legs (N=1 only, after the metric's timed region): a leg whose estimated "
                          "cost no longer fits is DROPPED and listed in secondary.dropped; 0 = no limit")
@@ -543,7 +555,7 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
     elapsed = max_over_ranks(local)   # the job's K steps = the slowest rank's (the closing barrier's own latency — one RCCL
                                       # all-reduce, ~0.1 ms, a fifth of 20 steps — is not part of anybody's steps)
 
-    if not FAKE:
+    if not FAKE and args.full:
         # the dominant kernel alone: KERNEL_LAUNCHES launches of k_rollout_fs between ONE HIP-event pair on the
         # launch stream (no per-launch events: a pair costs ~6 us of stream time), through the C-ABI directly
         draw = box["draw"]
@@ -585,7 +597,7 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
         del fills
 
     long_run = python_api = None
-    if not FAKE and world == 1 and not args.no_secondary:
+    if args.full and not FAKE and world == 1 and not args.no_secondary:
         # self-check of `value` on a region long enough for any outside observer (the default K = 20 steps last 0.5 ms):
         # 2000 steps of the same one_step, host-timed the same way
         torch.cuda.synchronize()
@@ -627,6 +639,7 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -656,7 +669,9 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
                      "not_counted_bytes_per_launch": LAST_ROW_BYTES * NUM_ENVS + 2 * 128 * NUM_ENVS
                                                      + (8 * rows if (not FAKE and fused_gae) else 0)},  # + advantages / targets
     }
-    if not FAKE:
+    if not args.full:   # a plain run has not timed the kernel alone: the figures above rest on kernel_ms
+        out["roofline"] = None
+    elif not FAKE:
         out["roofline"]["plain_fill"] = {"bytes": written, "ms": fill_ms, "GB/s": written / (fill_ms * 1e-3) / 1e9,
                                          "kernel_over_fill": kern_ms / fill_ms,
                                          "what": "torch fill_ of the bytes one launch writes, same box, same rotation: the device's store ceiling"}
@@ -671,8 +686,8 @@ def bench_rollout(args, torch, dev, rank, world, barrier, max_over_ranks, dist=N
         out["long_run"] = long_run
         out["python_api"] = python_api
     if rank == 0:
-        out["cpu_baseline"] = cpu_baseline(keys, values) if (world == 1 and not args.no_cpu_baseline and not FAKE) else None
-        if world == 1 and not FAKE and not args.no_secondary:
+        out["cpu_baseline"] = cpu_baseline(keys, values) if (args.full and world == 1 and not args.no_cpu_baseline and not FAKE) else None
+        if args.full and world == 1 and not FAKE and not args.no_secondary:
             del trajs, advs, tgts, ptrs   # 433 MB + of rotating buffers: not needed by the policy path
             try:
                 out["secondary"] = bench_secondary(torch, dev, args.secondary_budget_s)

@@ -13,4 +13,4 @@ fi
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee $OUT/smoke.txt
 echo "== bench"
-timeout 600 python bench.py --steps 200 --warmup 20 2>&1 | tail -3 | tee $OUT/bench.json
+timeout 600 python bench.py --full --steps 200 --warmup 20 2>&1 | tail -3 | tee $OUT/bench.json

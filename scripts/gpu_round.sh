@@ -13,7 +13,7 @@ tail -8 $OUT/pytest_gpu_full.txt | tee $OUT/pytest_gpu.txt
 echo "== smoke" | tee -a $OUT/summary.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.txt
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 600 python bench.py --steps 200 --warmup 20 2>/dev/null | tail -1 | tee $OUT/bench.json
+timeout 600 python bench.py --full --steps 200 --warmup 20 2>/dev/null | tail -1 | tee $OUT/bench.json
 echo "== rocprofv3 kernel trace" | tee -a $OUT/summary.txt
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/prof_trace.log 2>&1
 find $OUT/prof_trace -name "*kernel_stats*.csv" | head -1 | xargs -r cat | head -20 | tee $OUT/kernel_stats.csv

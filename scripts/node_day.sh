@@ -6,7 +6,7 @@
 #                                                 tests/test_multi_gpu_rccl.py::test_node_day_script_dry_run
 # Steps (each leaves a file; a failing step is recorded and the script goes on):
 #   1  the RCCL tests that SKIP below 2 GPUs (tests/test_multi_gpu_rccl.py, the two-rank tests of tests/test_gpu_parity.py)
-#   2  bench.py --gpus 1, 2, 4, 8 (the BASELINE metric, weak scaling: rollout shards, no data-path collective)
+#   2  bench.py --full --gpus 1, 2, 4, 8 (the BASELINE metric, weak scaling: rollout shards, no data-path collective)
 #   3  bench.py --gpus N --config ppo with the gradient step "flat" and "sharded" (configs[4]: RCCL nodes inside the step's hipGraph)
 #   4  scripts/allreduce_graph_probe.py: the 14.7 MB all-reduce and the sharded form's buckets inside a graph — the number DESIGN §7's
 #      0.42 ms-per-step estimate rests on
@@ -31,7 +31,7 @@ tail -3 "$OUT/pytest_rccl.txt" | tee -a "$OUT/summary.txt"
 
 step "2 bench.py --gpus $GPUS_LIST"
 for g in $GPUS_LIST; do
-  EXTRA=""; [ $g -gt 1 ] && EXTRA="--no-cpu-baseline"
+  EXTRA="--full"; [ $g -gt 1 ] && EXTRA="--full --no-cpu-baseline"
   timeout -k 10 900 $PY bench.py --gpus $g --steps 200 --warmup 20 $EXTRA 2> "$OUT/bench_gpus$g.err" | tail -1 > "$OUT/bench_gpus$g.json"
   $PY -c "import json,sys; d=json.load(open('$OUT/bench_gpus$g.json')); print('  gpus', d['n_gpus'], 'value %.4g' % d['value'], d['unit'], 'ms/step %.4f' % d['ms_per_step'], d.get('ranks_backend'))" 2>&1 | tee -a "$OUT/summary.txt"
 done

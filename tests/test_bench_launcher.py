@@ -34,6 +34,18 @@ def test_gpus_2_starts_two_ranks_and_prints_one_line():
     assert max(r["local_ms_per_step"] for r in out["ranks"]) == out["ms_per_step"]
 
 
+def test_full_is_an_option_and_off_by_default():
+    plain = run(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    full = run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
+    assert plain.returncode == 0 and full.returncode == 0, plain.stderr[-2000:] + full.stderr[-2000:]
+    p, f = json.loads(plain.stdout.strip().splitlines()[-1]), json.loads(full.stdout.strip().splitlines()[-1])
+    assert p["full"] is False and f["full"] is True
+    assert p["roofline"] is None and p["cpu_baseline"] is None and "secondary" not in p and "long_run" not in p
+    assert f["roofline"]["bound"] == "hbm"
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert p[k] == f[k], k
+
+
 def test_single_rank_default_and_world_size_mismatch():
     r = run(["--steps", "2", "--warmup", "0"])
     assert r.returncode == 0, r.stderr[-2000:]

@@ -44,7 +44,7 @@ def test_bench_gpus_2_over_rccl_lists_two_distinct_devices():
 def test_bench_gpus_2_gloo_rehearsal_on_one_gpu():
     """The same N-rank control flow on THIS box's single GPU (gloo control plane, ranks sharing the device): the launcher,
     per-rank shards, barrier + max-over-ranks, the `ranks` records — labelled as a rehearsal, never as an RCCL run."""
-    r, out = _bench(["--gpus", "2", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-secondary"],
+    r, out = _bench(["--gpus", "2", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary"],
                     BRL_BENCH_BACKEND="gloo")
     assert r.returncode == 0 and out is not None, r.stderr[-3000:]
     assert out["n_gpus"] == 2 and out["ranks_backend"].startswith("gloo") and len(out["ranks"]) == 2
@@ -157,7 +157,7 @@ def test_bench_control_flow_over_rccl_at_world_1():
     """The N-rank control flow of `bench.py` (process-group set-up with the device bound, barriers, MAX over ranks of the step time,
     the per-rank records gathered with all_gather_object) really over RCCL with one peer (BRL_FORCE_DIST=1): what the driver's N > 1
     runs execute besides the step itself."""
-    r, out = _bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-secondary"], BRL_FORCE_DIST="1")
+    r, out = _bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary"], BRL_FORCE_DIST="1")
     assert r.returncode == 0 and out is not None, r.stderr[-3000:]
     assert out["n_gpus"] == 1 and out["ranks_backend"].startswith("RCCL") and len(out["ranks"]) == 1 and "ranks_error" not in out
     assert out["value"] > 0 and out["roofline"]["frac"] > 0.05
