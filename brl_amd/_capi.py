@@ -160,6 +160,7 @@ def lib() -> C.CDLL:
                                      _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
     }
     sigs.update(sl_signatures())
+    sigs.update(league_signatures())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -184,6 +185,20 @@ def sl_signatures() -> dict:
         "brl_sl_sample": [i32, _vp, _vp, i64, u64, i64, _vp, _vp, _vp],
         "brl_sl_replay": [i32, _vp, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp],
         "brl_sl_loss": [i32, _vp, i64, _vp, _vp, i64, f32, _vp, _vp, _vp, i64, _vp],
+    }
+
+
+class LeagueNet(C.Structure):
+    """brl_league_net (include/brl_league.h): one "DeepMind" fp32 network by reference, 20 device pointers"""
+    _fields_ = [("w", _vp * 8), ("b", _vp * 8), ("actor_w", _vp), ("actor_b", _vp), ("critic_w", _vp), ("critic_b", _vp)]
+
+
+def league_signatures() -> dict:
+    """argtypes of include/brl_league.h (the batched league evaluation; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_league_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
+        "brl_league_forward": [i32, _vp, i64, i32, i64, i32, _vp, _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
     }
 
 

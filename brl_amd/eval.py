@@ -1,0 +1,40 @@
+"""One duplicate match between two saved models — the reference's ``eval.py``.
+
+    python -m brl_amd.eval team1_model_path=a.pt team2_model_path=b.pkl [team2_model_type=FAIR] [num_eval_envs=100] [dds_path=...]
+
+The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
+``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``."""
+from __future__ import annotations
+
+import sys
+
+EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
+    team1_model_path=None, team2_model_path=None, team1_activation="relu", team1_model_type="DeepMind",
+    team2_activation="relu", team2_model_type="DeepMind", num_eval_envs=100,
+    dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
+)
+
+
+def main(argv, log=print):
+    import brl_amd
+    from .checkpoint import load_params
+    from .evaluation import make_simple_duplicate_evaluate
+    from .league import parse
+    cfg = parse(argv, EVAL_DEFAULTS)
+    if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
+        raise SystemExit("team1_model_path= and team2_model_path= are required")
+    env = brl_amd.BridgeBidding(cfg["dds_path"])
+    duplicate_evaluate = make_simple_duplicate_evaluate(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                                        cfg["team2_model_type"], cfg["num_eval_envs"])
+    log(f"num envs: {cfg['num_eval_envs']}")
+    team1 = load_params(cfg["team1_model_path"], cfg["team1_activation"], cfg["team1_model_type"], env.device)
+    team2 = load_params(cfg["team2_model_path"], cfg["team2_activation"], cfg["team2_model_type"], env.device)
+    log("---------------------------------------------------")
+    log(f'{cfg["team1_model_path"]} vs. {cfg["team2_model_path"]}')
+    (imp, se, _), _, _ = duplicate_evaluate(team1, team2, 0)
+    log(f"IMP: {float(imp)} ± {float(se)}")
+    return float(imp), float(se)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

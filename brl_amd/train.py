@@ -46,6 +46,8 @@ DEFAULTS = dict(  # ppo.py:122-180 (PPOConfig), same names and defaults
     memoize_eval=True, memoize_eval_check_every=0,   # the per-iteration duplicate evaluations: play each distinct pair once (train())
     grad_allreduce="flat",      # the gradient step under a process group: "flat" | "sharded" (brl_amd/fused_update.py)
     check_rank_sync=True,       # under a process group: a parameter checksum compared across the ranks after every update
+    league_eval="loop",         # PFSP's league of the learner against the pool: "loop" (one evaluation per checkpoint) | "batched"
+                                # (brl_amd/league.py: all of them as one batched match)
 )
 
 
@@ -268,6 +270,9 @@ def train(config, log=print, on_rollout=None):
     pool_dir = os.path.join(config["log_path"], config["exp_name"], config["save_model_path"])
     if config["save_model"] and rank == 0:
         os.makedirs(pool_dir, exist_ok=True)                                                         # ppo.py:339-346
+    if config["league_eval"] not in ("loop", "batched"):
+        raise ValueError(f"league_eval {config['league_eval']!r}: 'loop' or 'batched'")
+    league_pool = {}   # league_eval="batched": the pool's checkpoints as loaded (a checkpoint file never changes once written)
     steps = 0
     history = []
     i = -1
@@ -321,6 +326,17 @@ def train(config, log=print, on_rollout=None):
             params_list = ckpt.list_checkpoints(pool_dir)[-int(config["num_model_zoo"]):]
 
             def league_imps():
+                if config["league_eval"] == "batched":
+                    from brl_amd.league import one_vs_many
+                    for name in params_list:
+                        if name not in league_pool:
+                            league_pool[name] = load_opponent(os.path.join(pool_dir, name), config["actor_activation"],
+                                                              config["actor_model_type"])
+                    for name in [k for k in league_pool if k not in params_list]:   # (left the window of num_model_zoo files)
+                        del league_pool[name]
+                    imp = one_vs_many(params, [league_pool[name] for name in params_list], eval_env, config["actor_activation"],
+                                      config["actor_model_type"], config["num_prioritized_envs"], rng_key=eval_rng, shard=sharded)
+                    return imp.to(torch.float64).cpu().numpy()
                 imps = np.zeros(len(params_list))
                 for k, name in enumerate(params_list):                                               # ppo.py:399-421
                     other = load_opponent(os.path.join(pool_dir, name), config["actor_activation"], config["actor_model_type"])
