@@ -161,6 +161,7 @@ def lib() -> C.CDLL:
     }
     sigs.update(sl_signatures())
     sigs.update(league_signatures())
+    sigs.update(boards_signatures())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -199,6 +200,16 @@ def league_signatures() -> dict:
     return {
         "brl_league_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
         "brl_league_forward": [i32, _vp, i64, i32, i64, i32, _vp, _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
+    }
+
+
+def boards_signatures() -> dict:
+    """argtypes of include/brl_boards.h (the board records; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_board_records": [i32, _vp, i64, _vp, _vp],
+        "brl_board_imp": [i32, _vp, _vp, i64, _vp, _vp],
+        "brl_board_keep_a": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp],
     }
 
 

@@ -1,9 +1,13 @@
 """One duplicate match between two saved models — the reference's ``eval.py``.
 
     python -m brl_amd.eval team1_model_path=a.pt team2_model_path=b.pkl [team2_model_type=FAIR] [num_eval_envs=100] [dds_path=...]
+                           [deals_path=deals.json|deals.pbn] [save_boards=out.json|out.pbn]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
-``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``."""
+``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
+``deals_path``: play the boards of a deal file (``boards.read_deals``; ``num_eval_envs`` is then their number) instead of
+dealing from the table; ``save_boards``: write every board's two auctions, contracts, scores and IMP (``boards.BoardRecords``).
+Without the two the output is what it always was."""
 from __future__ import annotations
 
 import sys
@@ -12,6 +16,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     team1_model_path=None, team2_model_path=None, team1_activation="relu", team1_model_type="DeepMind",
     team2_activation="relu", team2_model_type="DeepMind", num_eval_envs=100,
     dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
+    deals_path=None, save_boards=None,
 )
 
 
@@ -23,15 +28,30 @@ def main(argv, log=print):
     cfg = parse(argv, EVAL_DEFAULTS)
     if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
         raise SystemExit("team1_model_path= and team2_model_path= are required")
-    env = brl_amd.BridgeBidding(cfg["dds_path"])
-    duplicate_evaluate = make_simple_duplicate_evaluate(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
-                                                        cfg["team2_model_type"], cfg["num_eval_envs"])
+    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None
+    deals = None
+    if cfg["deals_path"] is not None:
+        from .boards import read_deals
+        deals = read_deals(cfg["deals_path"])
+        cfg["num_eval_envs"] = deals.n
+    env = brl_amd.BridgeBidding(cfg["dds_path"]) if deals is None else brl_amd.BridgeBidding(lut=(deals.lut_keys(), deals.lut_values()))
     log(f"num envs: {cfg['num_eval_envs']}")
     team1 = load_params(cfg["team1_model_path"], cfg["team1_activation"], cfg["team1_model_type"], env.device)
     team2 = load_params(cfg["team2_model_path"], cfg["team2_activation"], cfg["team2_model_type"], env.device)
     log("---------------------------------------------------")
     log(f'{cfg["team1_model_path"]} vs. {cfg["team2_model_path"]}')
-    (imp, se, _), _, _ = duplicate_evaluate(team1, team2, 0)
+    if boards_run:
+        from .boards import make_board_match
+        board_match = make_board_match(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                       cfg["team2_model_type"], cfg["num_eval_envs"])
+        (imp, se, _), records = board_match(team1, team2, deals if deals is not None else 0)
+        if cfg["save_boards"] is not None:
+            records.save(cfg["save_boards"])
+            log(f"boards: {cfg['save_boards']}")
+    else:
+        duplicate_evaluate = make_simple_duplicate_evaluate(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                                            cfg["team2_model_type"], cfg["num_eval_envs"])
+        (imp, se, _), _, _ = duplicate_evaluate(team1, team2, 0)
     log(f"IMP: {float(imp)} ± {float(se)}")
     return float(imp), float(se)
 

@@ -322,9 +322,11 @@ class _ActiveRows:
 
 
 def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward, tables, stats, bid_set, cum_return,
-               rewards_sum, sync_every, record_actions=None, record_logits=None, by_turn=False, record_calls=None):
+               rewards_sum, sync_every, record_actions=None, record_logits=None, by_turn=False, record_calls=None, after_step=None):
     """Runs ``brl_eval_step`` until every board is finished; ``state.packed`` is advanced in place.  (``sync_every`` — how often
-    the loop condition used to be read back — is kept in the signatures and ignored: see ``_DoneWatch``.)"""
+    the loop condition used to be read back — is kept in the signatures and ignored: see ``_DoneWatch``.)  ``after_step(packed,
+    action)``: called behind every step launch with the tables as stepped and the calls made (boards.py keeps table A's final
+    state with it: the launch that ends table A re-deals the slot for table B)."""
     n, dev = state.num_envs, env.device
     obs = state.observation
     term = torch.empty(n, dtype=torch.bool, device=dev)
@@ -364,6 +366,8 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
                 C.byref(ps) if ps is not None else None, int(bid_set),
                 ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
             obs = nobs
+            if after_step is not None:
+                after_step(packed, action)
             if record_actions is not None:
                 record_actions.append(action.clone())
             watch.post(count, term)
@@ -384,6 +388,8 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
                 C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
                 C.byref(ps) if ps is not None else None, int(bid_set),
                 ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, ptr(obs_f32), stream()))
+            if after_step is not None:
+                after_step(packed, action)
             if record_calls is not None:   # (the calls of THIS loop — -1: the board waited for its team's iteration — for oracle replays)
                 record_calls.append(action.clone())
             obs = nobs
@@ -408,6 +414,8 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
             C.byref(ps) if ps is not None else None, int(bid_set),
             ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
         obs = nobs
+        if after_step is not None:
+            after_step(packed, action)
         if record_actions is not None:
             record_actions.append(action.clone())
         watch.post(count, term)
