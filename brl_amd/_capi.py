@@ -162,6 +162,7 @@ def lib() -> C.CDLL:
     sigs.update(sl_signatures())
     sigs.update(league_signatures())
     sigs.update(boards_signatures())
+    sigs.update(book_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -210,6 +211,15 @@ def boards_signatures() -> dict:
         "brl_board_records": [i32, _vp, i64, _vp, _vp],
         "brl_board_imp": [i32, _vp, _vp, i64, _vp, _vp],
         "brl_board_keep_a": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp],
+    }
+
+
+def book_argtypes() -> dict:
+    """argtypes of include/brl_book.h (the bidding-system book; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_book_samples": [i32, _vp, i64, _vp, i32, i32, _vp, _vp, _vp],
+        "brl_book_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp],
     }
 
 

@@ -2,12 +2,15 @@
 
     python -m brl_amd.eval team1_model_path=a.pt team2_model_path=b.pkl [team2_model_type=FAIR] [num_eval_envs=100] [dds_path=...]
                            [deals_path=deals.json|deals.pbn] [save_boards=out.json|out.pbn]
+                           [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
 ``deals_path``: play the boards of a deal file (``boards.read_deals``; ``num_eval_envs`` is then their number) instead of
 dealing from the table; ``save_boards``: write every board's two auctions, contracts, scores and IMP (``boards.BoardRecords``).
-Without the two the output is what it always was."""
+``save_book``: write the bidding-system book of the match (``book.system_book``: what each call shows, by auction prefix, over
+the first ``book_depth`` calls; entries with fewer than ``book_min_count`` samples are left out) as JSON or, ``.txt``, as a tree.
+Without these arguments the output is what it always was."""
 from __future__ import annotations
 
 import sys
@@ -16,7 +19,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     team1_model_path=None, team2_model_path=None, team1_activation="relu", team1_model_type="DeepMind",
     team2_activation="relu", team2_model_type="DeepMind", num_eval_envs=100,
     dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
-    deals_path=None, save_boards=None,
+    deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20,
 )
 
 
@@ -28,7 +31,7 @@ def main(argv, log=print):
     cfg = parse(argv, EVAL_DEFAULTS)
     if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
         raise SystemExit("team1_model_path= and team2_model_path= are required")
-    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None
+    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -48,6 +51,10 @@ def main(argv, log=print):
         if cfg["save_boards"] is not None:
             records.save(cfg["save_boards"])
             log(f"boards: {cfg['save_boards']}")
+        if cfg["save_book"] is not None:
+            from .book import system_book
+            system_book(records, int(cfg["book_depth"])).save(cfg["save_book"], min_count=int(cfg["book_min_count"]))
+            log(f"book: {cfg['save_book']}")
     else:
         duplicate_evaluate = make_simple_duplicate_evaluate(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
                                                             cfg["team2_model_type"], cfg["num_eval_envs"])
