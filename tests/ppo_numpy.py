@@ -161,37 +161,76 @@ def fair_params_of(net):
     return [(l.weight.detach().cpu().double().numpy().copy(), l.bias.detach().cpu().double().numpy().copy()) for l in lins]
 
 
-def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae, tgt, activation="relu"):
-    """-> (total, aux, grads like params): the loss of `head_loss` on the FAIR forward pass and its gradient by reverse-mode
-    differentiation of the reference's own statement order (a tape of (kind, ...) entries; no shared code with the build)."""
-    act, dact = _act(activation)
+def fair_forward(params, obs, activation="relu", gate_fn=None):
+    """the FAIR forward pass in the reference's statement order -> (logits, value, x, tape): x = the heads' input, tape = the
+    (kind, ...) entries `fair_loss_and_grads` differentiates in reverse.
+
+    gate_fn(site, z, layer, h_in, shortcut) (ReLU only) returns the 0/1 gate of activation site `site` instead of z > 0; the
+    activation's output is then z * gate and its derivative the gate itself.  A checker of a fp32 step takes the step's own gate
+    where z is within the step's rounding of 0.  The twelve sites are the twelve `activate(...)` calls below, in order:
+
+        site   0   1   2   3*  4   5   6   7   8   9*  10  11
+        layer  0   1   2   2   3   4   6   7   8   8   9   10      (the output the FusedFair step keeps of it:
+        output h0  h1  h2  g1  h3  h4  h6  h7  h8  g3  h9  h10      tests/test_gpu_update_float64.FAIR_SITES)
+
+    What the rounding band of a site needs comes with the call.  Behind a linear layer (every site but 3 and 9) z = h_in W^T + b
+    with (W, b) = params[layer], h_in that layer's input (layer 6: [z5 | obs]) and shortcut None: a fp32 product sum is off by a
+    small multiple of 2^-24 of the sum of its terms' magnitudes, so the band is c (|h_in| |W|^T + |b|); the checkers use c = 4e-6,
+    ~70 ulp, as for the DeepMind MLP.  At the residual sums (*) z = act(h_in W^T + b) + shortcut, with `layer` the linear layer
+    FEEDING the sum (2: h2 = act(h1 W_2^T + b_2), 8: h8 likewise), h_in its input and shortcut the pre-activation z0 / z6 taken
+    right behind layer 0 / 6.  ReLU is 1-Lipschitz, so h2 carries no more error than its pre-activation, c (|h_in| |W|^T + |b|);
+    the shortcut arrives with a relative error of the same few ulp, c |shortcut|, and the fp32 addition rounds by 2^-24 (|h2| +
+    |shortcut|), which both terms already cover.  Band of the sum: c (|h_in| |W|^T + |b| + |shortcut|).  (The shortcut's own
+    accumulation error — 48 or so terms of a 0/1 observation, ~1e-7 absolute — is far below the first term, a 200-term sum of
+    O(1) magnitude.)"""
+    act, _ = _act(activation)
+    gated = activation == "relu" and gate_fn is not None
     x = obs.astype(np.float64)
     inp = x
     tape = []
+    site = [0]
+    last = [None, None]      # (layer, input) of the last linear layer
 
     def lin(k, v):
         tape.append(("lin", k, v))
+        last[0], last[1] = k, v
         return v @ params[k][0].T + params[k][1]
 
-    def activate(v):
-        out = act(v)
-        tape.append(("act", out))
+    def activate(v, shortcut=None):
+        if gated:
+            gate = np.asarray(gate_fn(site[0], v, last[0], last[1], shortcut), dtype=bool)
+            out = np.where(gate, v, 0.0)
+            tape.append(("act", out, gate.astype(np.float64)))
+        else:
+            out = act(v)
+            tape.append(("act", out, None))
+        site[0] += 1
         return out
 
     x = lin(0, x); s1 = x
     x = activate(x); x = lin(1, x); x = activate(x); x = lin(2, x); x = activate(x)
     x = x + s1; tape.append(("add", "s1")); s2 = x
-    x = activate(x); x = lin(3, x); x = activate(x); x = lin(4, x); x = activate(x)
+    x = activate(x, s1); x = lin(3, x); x = activate(x); x = lin(4, x); x = activate(x)
     x = x + s2; tape.append(("add", "s2"))
     x = lin(5, x)
     x = np.concatenate([x, inp], axis=-1); tape.append(("cat", 200))
     x = lin(6, x); s3 = x
     x = activate(x); x = lin(7, x); x = activate(x); x = lin(8, x); x = activate(x)
     x = x + s3; tape.append(("add", "s3")); s4 = x
-    x = activate(x); x = lin(9, x); x = activate(x); x = lin(10, x); x = activate(x)
+    x = activate(x, s3); x = lin(9, x); x = activate(x); x = lin(10, x); x = activate(x)
     x = x + s4; tape.append(("add", "s4"))
+    assert site[0] == 12
     logits = x @ params[11][0].T + params[11][1]
     value = (x @ params[12][0].T + params[12][1])[:, 0]
+    return logits, value, x, tape
+
+
+def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae, tgt, activation="relu", gate_fn=None):
+    """-> (total, aux, grads like params): the loss of `head_loss` on the FAIR forward pass (`fair_forward`; gate_fn: see there)
+    and its gradient by reverse-mode differentiation of the reference's own statement order (a tape of (kind, ...) entries; no
+    shared code with the build)."""
+    _, dact = _act(activation)
+    logits, value, x, tape = fair_forward(params, obs, activation, gate_fn)
     total, aux, dlogits, dv = head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tgt)
     grads = [None] * len(params)
     grads[11] = (dlogits.T @ x, dlogits.sum(0))
@@ -210,7 +249,7 @@ def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob,
                     d = d + pending.pop(later)
                     pending[name] = d.copy()
         elif entry[0] == "act":
-            d = d * dact(entry[1])
+            d = d * (dact(entry[1]) if entry[2] is None else entry[2])
         elif entry[0] == "cat":
             d = d[:, :entry[1]]
         else:

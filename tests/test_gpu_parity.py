@@ -2116,7 +2116,8 @@ def test_fused_fair_step_matches_numpy_restatement(activation, rscale, masked, c
     at minibatch 1024 vs the float64 numpy restatement (tests/ppo_numpy.py::fair_loss_and_grads, itself checked against autograd in
     float64 on the CPU): every gradient before the sweep, the losses, the pre-clip norm, every parameter after the first Adam step.
     chain: forward + loss + backward chain as ONE launch (brl_fair_chain, the default) / as ~55 launches (library products +
-    brl_mlp_gemm + elementwise kernels)."""
+    brl_mlp_gemm + elementwise kernels).  (Perturbed ReLU networks, later Adam steps and other minibatch sizes:
+    tests/test_gpu_update_float64.py::test_fused_fair_step_matches_float64.)"""
     _check_fused_fair_step(activation, rscale, masked, chain, 0.0)
 
 

@@ -2,10 +2,14 @@
 
 ``FusedMinibatch`` (the default step of the DeepMind MLPs, brl_amd/fused_update.py) writes its backward pass out by hand: the head's
 dW / db ride in extra workgroups of the dz chain, the weight gradients are one grouped bf16x3 launch, the bias gradients are tile sums
-that the clip + Adam launch finishes.  Here every gradient it leaves in its flat buffer, its pre-clip norm, its logged losses and the
-parameters / moments after three successive Adam steps are compared with the float64 restatement tests/ppo_numpy.py (itself checked
-against torch autograd in float64 by tests/test_update_cpu.py), for every switch that changes the code path inside the step.  Also:
-the FAIR network's inference forward (brl_fair_forward) after updates on each update path."""
+that the clip + Adam launch finishes.  ``FusedFair`` (the FAIR residual net's step) is the other hand-written backward pass: forward,
+loss and the whole backward chain of 16 rows per workgroup out of LDS (brl_fair_chain), the twelve weight gradients as one grouped
+launch, one launch for every bias gradient; or, by minibatch size and switch, the same launch by launch on brl_mlp_gemm or on library
+products.  Here every gradient either step leaves in its flat buffer, its pre-clip norm, its logged losses and the parameters / moments
+after three successive Adam steps are compared with the float64 restatement tests/ppo_numpy.py (itself checked against torch autograd
+in float64 by tests/test_update_cpu.py), for every switch and minibatch size that changes the code path inside the step
+(test_fused_deepmind_step_matches_float64, test_fused_fair_step_matches_float64).  Also: the FAIR network's inference forward
+(brl_fair_forward) after updates on each update path."""
 import numpy as np
 import pytest
 import torch
@@ -156,6 +160,180 @@ def test_fused_deepmind_step_matches_float64(case):
                 worst_m = max(worst_m, np.abs(_np(opt_state["opt"].state[q]["exp_avg"]) - mm).max())
                 worst_v = max(worst_v, np.abs(_np(opt_state["opt"].state[q]["exp_avg_sq"]) - vv).max())
                 moved = max(moved, np.abs(a - a0).max())
+        assert worst_p < 0.02 * lr_t and moved > 0.3 * lr_t, (t, worst_p, moved, lr_t, gn)
+        assert worst_m < 2e-5 * gc + 1e-12, (t, worst_m, gc)
+        assert worst_v < 4e-8 * gc * gc + 1e-6 * vmax, (t, worst_v, gc, vmax)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# FusedFair: (activation, minibatch, config overrides, (fm.chain, fm.own_gemm) the case must run on, seed of its batches)
+# ---------------------------------------------------------------------------------------------------------------
+FAIR_CASES = {
+    "relu_chain": ("relu", 1024, {}, (True, True), 500),                       # brl_fair_chain, 64 workgroups
+    "tanh_chain": ("tanh", 1024, {}, (True, True), 500),
+    "B16": ("relu", 16, {}, (True, True), 510),                                # one workgroup
+    "B48": ("relu", 48, {}, (True, True), 520),                                # 3 workgroups, under one 64-row tile
+    "B1008": ("relu", 1008, {}, (True, True), 530),                            # 63 workgroups, a K tail of the grouped dW launch
+    "launches": ("relu", 1024, {"fair_chain": False}, (False, True), 500),     # launch by launch, brl_mlp_gemm GATE_COLSUM
+    "B100": ("relu", 100, {}, (False, True), 540),                             # B % 16: no chain; B % 4 == 0: own GEMM
+    "B1000_tanh": ("tanh", 1000, {}, (False, True), 550),
+    "B333": ("relu", 333, {}, (False, False), 560),                            # library products, brl_act_bwd_colsum
+    "no_own_gemm": ("relu", 1024, {"fair_chain": False, "own_gemm": False}, (False, False), 500),
+    "reward_scaling": ("relu", 1024, {"reward_scaling": True}, (True, True), 500),
+    "unmasked": ("relu", 1024, {"actor_illegal_action_mask": False}, (True, True), 500),
+    "no_value_clipping": ("relu", 1024, {"value_clipping": False}, (True, True), 500),
+    "no_global_clipping": ("relu", 1024, {"global_gradient_clipping": False}, (True, True), 500),
+    "illegal_coef": ("relu", 1024, {"illegal_action_l2norm_coef": 0.5}, (False, True), 500),
+    "anneal_lr": ("relu", 1024, {"anneal_lr": True, "num_minibatches": 1, "num_updates": 4}, (True, True), 500),
+}
+# the twelve activation outputs in the order of tests/ppo_numpy.fair_forward's sites; FusedFair keeps every one (fair_stored_gates)
+FAIR_SITES = ("h0", "h1", "h2", "g1", "h3", "h4", "h6", "h7", "h8", "g3", "h9", "h10")
+FAIR_PERTURB_SEED = 21
+AMBIGUOUS_CAP = 1e-4      # of B x 12 x 200 activations per step
+KINK_CAP = 2              # samples per step, of each kind
+
+
+def fair_case(case, device):
+    """-> (activation, B, cfg, expected (chain, own_gemm), seed, forward pass, its network on `device`): `init(4)` with N(0, 0.01)
+    added to every weight and N(0, 0.1) to every bias — under ReLU too: hk.Linear's zero biases would hide a bias the step never
+    adds, or adds from the wrong layer.  (Drawn on the host, so the CPU check of the cases' inputs sees the same network.)"""
+    from brl_amd.models import make_forward_pass
+    from tests.test_update_cpu import CFG
+    activation, B, over, path, seed = FAIR_CASES[case]
+    cfg = dict(CFG, lr=LR, minibatch_size=B, update_epochs=1, graph_update=True, **over)
+    fp = make_forward_pass(activation, "FAIR")
+    net = fp.init(4)
+    gen = torch.Generator().manual_seed(FAIR_PERTURB_SEED)
+    with torch.no_grad():
+        for q in net.parameters():
+            q.add_(torch.randn(q.shape, generator=gen) * (0.1 if q.dim() == 1 else 0.01))
+    return activation, B, cfg, path, seed, fp, net.to(device)
+
+
+def fair_gate_fn(P, stored, ambiguous):
+    """a gate_fn for tests/ppo_numpy.fair_forward (its docstring derives the bands): z > 0, except where |z| is within 4e-6 of the
+    magnitude sum behind it — there the gate is stored[site] (the fp32 step's own; None: z > 0 all the same) and ambiguous[0]
+    counts the entry"""
+    def gate_fn(site, z, layer, h_in, shortcut):
+        band = np.abs(h_in) @ np.abs(P[layer][0]).T + np.abs(P[layer][1])
+        if shortcut is not None:
+            band = band + np.abs(shortcut)
+        amb = np.abs(z) < 4e-6 * band
+        gate = z > 0
+        if amb.any():
+            ambiguous[0] += int(amb.sum())
+            if stored is not None:
+                gate[amb] = stored[site][amb]
+        return gate
+    return gate_fn
+
+
+def fair_stored_gates(fm):
+    """the step's own ReLU gates, one [B, 200] bool array per site of FAIR_SITES, rows in the step's permuted order: h0, h1, g1, h3,
+    h6, h7, g3, h9 are inputs of square layers (the stacked `inp` buffer, fm.t[...]); h2, h4, h8, h10 are fm.gates on the chain
+    path and fm.t[...] launch by launch"""
+    chain_gates = {"h2": 0, "h4": 1, "h8": 2, "h10": 3}
+    return [((fm.gates[chain_gates[name]] if fm.chain and name in chain_gates else fm.t[name]) > 0).cpu().numpy() for name in FAIR_SITES]
+
+
+def fair_input_conditions(cfg, P, args, activation, stored=None):
+    """the two conditions on a step's INPUTS, from float64 alone where stored is None -> (ambiguous ReLU entries, samples at the
+    ratio kink, samples at the value kink, the gate_fn for the gradient pass)"""
+    from tests.ppo_numpy import fair_forward
+    ambiguous = [0]
+    gate_fn = fair_gate_fn(P, stored, ambiguous) if activation == "relu" else None
+    logits, value, _, _ = fair_forward(P, args[0], activation, gate_fn)
+    n_ratio, n_value = _ppo_kinks(cfg, logits, value, args[1].astype(bool), args[2], args[3], args[4])
+    return ambiguous[0], n_ratio, n_value, gate_fn
+
+
+@pytest.mark.parametrize("case", list(FAIR_CASES))
+def test_fused_fair_step_matches_float64(case):
+    """The twin of test_fused_deepmind_step_matches_float64 for FusedFair: three successive update_step calls, each ONE minibatch step,
+    the float64 reference (tests/ppo_numpy.fair_loss_and_grads + adam_step) of step t starting from the GPU's own parameters and
+    moments before it, rows in the step's own order (fm.perm).  One case per line of the step's code paths — the one-launch chain
+    at 64, 1, 3 and 63 workgroups (B = 16: a single workgroup; 48: less than one 64-row tile; 1008: the grouped dW launch sums over
+    a K tail and brl_bias_finalize_rows finishes a workgroup count that is no multiple of 4), launch by launch on brl_mlp_gemm
+    (B % 16 != 0 or fair_chain=False), library products (B % 4 != 0 or own_gemm=False), every switch of the loss and of the sweep —
+    and each asserts the path it ran on.  EVERY case perturbs every parameter (fair_case), ReLU included, so no bias is zero.
+    After each call, with the project's bounds (the DeepMind test's docstring derives them):
+      * the five logged losses within 2e-5 (+ coef 2e-6 sigma_1 with the illegal-action term), the logged norm / 2 within 1e-4 relative;
+      * all thirteen (W, b) gradients left in the flat buffer (the `.grad` views; on the chain path the heads also as the [39, 200]
+        block the grouped launch writes) within 2e-5 max|gW| + 1e-9; fm.norm within 1e-4 relative;
+      * every step counter t; lr_dev and the optimizer's rate lr_t;
+      * parameters within 0.02 lr_t of adam_step(t) (and moved by > 0.3 lr_t), exp_avg within 2e-5 gc + 1e-12, exp_avg_sq within
+        4e-8 gc^2 + 1e-6 max|v|, gc the largest clipped gradient: a moment slot mapped to another parameter of FAIR's flat layout
+        (square layers, W0, W6, heads, biases), or a wrong bias correction at t >= 2, fails here.
+    ReLU gates: where a float64 pre-activation is within its fp32 rounding band of 0 (fair_gate_fn) the gate is the step's own
+    (fair_stored_gates, read with > 0); such entries are at most 1e-4 of B x 12 x 200, samples at PPO's clip kinks at most 2 of each
+    kind per step — conditions on the inputs, which tests/test_update_cpu.py checks for every case's seeds without a GPU."""
+    from brl_amd.roll_out import Transition
+    from brl_amd.update import FusedFair, make_optimizer, make_update_step
+    from tests.ppo_numpy import adam_step, fair_loss_and_grads, fair_params_of
+    from tests.test_update_cpu import fake_batch
+    activation, B, cfg, (want_chain, want_own), seed, fp, net = fair_case(case, "cuda")
+    opt_state = make_optimizer(cfg, net)
+    rs = (net, opt_state, None, None, 0, 9)
+    lins = list(net.l) + [net.actor, net.critic]
+    H = lins[0].weight.shape[0]
+    upd = make_update_step(cfg, fp)
+    for t in (1, 2, 3):
+        tb, adv, tgt = fake_batch(1, B, seed=seed + t)
+        lr_t = LR * (1.0 - (t - 1) / cfg["num_updates"]) if cfg.get("anneal_lr") else LR
+        assert abs(opt_state["opt"].param_groups[0]["lr"] - lr_t) < 1e-12
+        P = fair_params_of(net)
+        st = opt_state["opt"].state
+        M = [tuple(_np(st[q]["exp_avg"]) if q in st else np.zeros(tuple(q.shape)) for q in (l.weight, l.bias)) for l in lins]
+        V = [tuple(_np(st[q]["exp_avg_sq"]) if q in st else np.zeros(tuple(q.shape)) for q in (l.weight, l.bias)) for l in lins]
+        rs, (total, aux) = upd(rs, Transition(*[x.cuda() for x in tb]), adv.cuda(), tgt.cuda())
+        opt_state = rs[1]
+        fm = opt_state.get("graphed")
+        assert isinstance(fm, FusedFair), opt_state.get("graph_error")
+        assert (fm.chain, fm.own_gemm) == (want_chain, want_own), (fm.chain, fm.own_gemm)
+        if fm.chain:
+            assert fm.group_dw and fm.cpartials.shape[0] == B // 16 == {"B16": 1, "B48": 3, "B1008": 63}.get(case, 64)
+        assert abs(float(fm.lr_dev[0]) - lr_t) < 1e-9
+        assert {int(s_["step"]) for s_ in opt_state["opt"].state.values()} == {t}
+        # the minibatch in the order the step gathered it (its stored activations are in that order)
+        perm = fm.perm[:B].cpu()
+        flat = Transition(*[x.reshape((B,) + x.shape[2:])[perm] for x in tb])
+        args = (flat.obs.numpy(), flat.legal_action_mask.numpy(), flat.action.numpy().astype(np.int64), flat.value.double().numpy(),
+                flat.log_prob.double().numpy(), adv.reshape(-1)[perm].double().numpy(), tgt.reshape(-1)[perm].double().numpy())
+        stored = fair_stored_gates(fm) if activation == "relu" else None
+        n_amb, n_ratio, n_value, gate_fn = fair_input_conditions(cfg, P, args, activation, stored)
+        assert n_ratio <= KINK_CAP and n_value <= KINK_CAP, (t, n_ratio, n_value)
+        assert n_amb <= AMBIGUOUS_CAP * B * len(FAIR_SITES) * H, (t, n_amb)
+        want_total, want_aux, G = fair_loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
+        ill = float(cfg.get("illegal_action_l2norm_coef", 0.0))
+        # every gradient the step left in the flat buffer (the sweep scales them in registers only)
+        gmax = max(np.abs(gw).max() for gw, _ in G)
+        errs = [(np.abs(_np(lin.weight.grad) - gw).max(), np.abs(_np(lin.bias.grad) - gb).max()) for lin, (gw, gb) in zip(lins, G)]
+        print(f"{case} t={t}: {n_amb} ambiguous gates, kinks {n_ratio}/{n_value}, total off by {abs(float(total[0, 0]) - want_total):.2e}, "
+              f"worst gradient error {max(max(e) for e in errs):.2e} of {2e-5 * gmax + 1e-9:.2e}")
+        assert abs(float(total[0, 0]) - want_total) < 2e-5 + ill * 2e-6 * want_aux[5], (t, float(total[0, 0]), want_total)
+        for k in range(5):
+            assert abs(float(aux[k][0, 0]) - want_aux[k]) < 2e-5, (t, k, float(aux[k][0, 0]), want_aux[k])
+        assert abs(float(aux[5][0, 0]) - want_aux[5]) < 1e-4 * want_aux[5], (t, float(aux[5][0, 0]), want_aux[5])
+        for k, (ew, eb) in enumerate(errs):
+            assert ew < 2e-5 * gmax + 1e-9 and eb < 2e-5 * gmax + 1e-9, (t, k, ew, eb, gmax)
+        if fm.chain:
+            eh = np.abs(_np(fm.GWh) - np.concatenate([G[11][0], G[12][0]])).max()
+            assert fm.GWh.shape == (39, H) and eh < 2e-5 * gmax + 1e-9, (t, eh, gmax)
+        P1, M1, V1, gn = adam_step(cfg, t, P, M, V, G, lr=lr_t)
+        assert abs(float(fm.norm[0]) - gn) < 1e-4 * gn, (t, float(fm.norm[0]), gn)
+        clip = min(1.0, cfg["max_grad_norm"] / (gn + 1e-6)) if cfg.get("global_gradient_clipping", True) else 1.0
+        gc = clip * max(max(np.abs(gw).max(), np.abs(gb).max()) for gw, gb in G)    # the largest clipped gradient, biases included
+        vmax = max(np.abs(v_).max() for pair in V1 for v_ in pair)
+        got = fair_params_of(net)
+        worst_p = worst_m = worst_v = moved = 0.0
+        for lin, p1, m1, v1, p0, p_ in zip(lins, P1, M1, V1, P, got):
+            for q, a, mm, vv, a0, b_ in zip((lin.weight, lin.bias), p1, m1, v1, p0, p_):
+                worst_p = max(worst_p, np.abs(b_ - a).max())
+                worst_m = max(worst_m, np.abs(_np(opt_state["opt"].state[q]["exp_avg"]) - mm).max())
+                worst_v = max(worst_v, np.abs(_np(opt_state["opt"].state[q]["exp_avg_sq"]) - vv).max())
+                moved = max(moved, np.abs(a - a0).max())
+        print(f"{case} t={t}: parameters off by {worst_p / lr_t:.4f} lr_t (moved {moved / lr_t:.2f}), exp_avg by {worst_m:.2e} of "
+              f"{2e-5 * gc + 1e-12:.2e}, exp_avg_sq by {worst_v:.2e} of {4e-8 * gc * gc + 1e-6 * vmax:.2e}")
         assert worst_p < 0.02 * lr_t and moved > 0.3 * lr_t, (t, worst_p, moved, lr_t, gn)
         assert worst_m < 2e-5 * gc + 1e-12, (t, worst_m, gc)
         assert worst_v < 4e-8 * gc * gc + 1e-6 * vmax, (t, worst_v, gc, vmax)

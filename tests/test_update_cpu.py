@@ -333,6 +333,76 @@ def test_fair_numpy_restatement_with_switches_matches_autograd_in_float64(activa
         assert np.abs(lin.weight.grad.numpy() - gw).max() < 1e-12 and np.abs(lin.bias.grad.numpy() - gb).max() < 1e-12
 
 
+def test_fair_restatement_gate_override():
+    """fair_loss_and_grads' gate_fn (how a checker of a fp32 step takes that step's own ReLU gates): it is asked at the twelve
+    activation sites in order, with the linear layer behind each and the shortcut at the two residual sums; the default gate given
+    back reproduces gate_fn=None bit for bit and still equals autograd in float64; one flipped gate at a residual sum changes the
+    gradients upstream of it"""
+    from brl_amd.update import ppo_loss
+    from tests.ppo_numpy import fair_loss_and_grads, fair_params_of
+    net = make_forward_pass("relu", "FAIR").init(3).double()
+    _perturb(net, 6)
+    flat, b64, adv, tgt, args = _batch64(48, seed=3)
+    P = fair_params_of(net)
+    t0, a0, G0 = fair_loss_and_grads(dict(CFG), P, *args)
+    seen = []
+
+    def default(site, z, layer, h_in, shortcut):
+        seen.append((site, layer, shortcut is not None))
+        pre = h_in @ P[layer][0].T + P[layer][1]
+        assert np.array_equal(z, pre if shortcut is None else np.maximum(pre, 0.0) + shortcut)
+        return z > 0
+    t1, a1, G1 = fair_loss_and_grads(dict(CFG), P, *args, gate_fn=default)
+    assert seen == [(s, l, s in (3, 9)) for s, l in enumerate((0, 1, 2, 2, 3, 4, 6, 7, 8, 8, 9, 10))]
+    assert t0 == t1 and a0 == a1
+    assert all(np.array_equal(a, c) and np.array_equal(b, d) for (a, b), (c, d) in zip(G0, G1))
+    logits, value = net(flat.obs.double())
+    total, _ = ppo_loss(dict(CFG), logits, value, b64, adv, tgt)
+    total.backward()
+    assert abs(float(total.detach()) - t1) < 1e-12
+    for lin, (gw, gb) in zip(list(net.l) + [net.actor, net.critic], G1):
+        assert np.abs(lin.weight.grad.numpy() - gw).max() < 1e-12 and np.abs(lin.bias.grad.numpy() - gb).max() < 1e-12
+
+    def flip(site, z, layer, h_in, shortcut):
+        g = z > 0
+        if site == 3:
+            g[7, 11] = ~g[7, 11]
+        return g
+    _, _, G2 = fair_loss_and_grads(dict(CFG), P, *args, gate_fn=flip)
+    assert np.abs(G0[0][1] - G2[0][1]).max() > 1e-9 and np.array_equal(G0[5][0], G2[5][0]) is False
+    # (tanh has no gate: the hook is not consulted)
+    assert fair_loss_and_grads(dict(CFG), P, *args, activation="tanh", gate_fn=flip)[0] == fair_loss_and_grads(dict(CFG), P, *args, activation="tanh")[0]
+
+
+def _fair_case_names():
+    from tests.test_gpu_update_float64 import FAIR_CASES
+    return list(FAIR_CASES)
+
+
+@pytest.mark.parametrize("case", _fair_case_names())
+def test_fair_float64_cases_meet_their_input_conditions(case):
+    """tests/test_gpu_update_float64.test_fused_fair_step_matches_float64 caps, per step, the ReLU pre-activations inside their fp32
+    rounding band (where it takes the GPU step's own gate) at 1e-4 of all and the samples at PPO's clip kinks at 2 of each kind.
+    Both are properties of the case's inputs — its seeded network and batches — so they are checked here in float64 alone, with
+    z > 0 in place of the stored gates and the parameters of steps 2 and 3 from the float64 Adam step rounded to fp32: a seed that
+    misses a cap is changed here, before the case ever runs on a GPU."""
+    from tests.ppo_numpy import adam_step, fair_loss_and_grads, fair_params_of
+    from tests.test_gpu_update_float64 import AMBIGUOUS_CAP, FAIR_SITES, KINK_CAP, LR, fair_case, fair_input_conditions
+    activation, B, cfg, _, seed, _, net = fair_case(case, "cpu")
+    P = fair_params_of(net)
+    M = [(np.zeros_like(W), np.zeros_like(b)) for W, b in P]
+    V = [(np.zeros_like(W), np.zeros_like(b)) for W, b in P]
+    for t in (1, 2, 3):
+        _, _, _, _, args = _batch64(B, seed=seed + t)
+        lr_t = LR * (1.0 - (t - 1) / cfg["num_updates"]) if cfg.get("anneal_lr") else LR
+        n_amb, n_ratio, n_value, gate_fn = fair_input_conditions(cfg, P, args, activation)
+        assert n_ratio <= KINK_CAP and n_value <= KINK_CAP, (t, n_ratio, n_value)
+        assert n_amb <= AMBIGUOUS_CAP * B * len(FAIR_SITES) * P[0][0].shape[0], (t, n_amb)
+        _, _, G = fair_loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
+        P, M, V, _ = adam_step(cfg, t, P, M, V, G, lr=lr_t)
+        P = [tuple(x.astype(np.float32).astype(np.float64) for x in pair) for pair in P]
+
+
 @pytest.mark.parametrize("clipping,max_norm", [(True, 0.5), (True, 1e3), (False, 0.5)])
 def test_adam_step_matches_torch_adam_in_float64(clipping, max_norm):
     """tests/ppo_numpy.adam_step — steps 1, 2 and 3 (bias-corrected, not sign-like after the first) — against
