@@ -8,6 +8,19 @@
 // table.  `cand`: the actions the distribution ranges over — the legal ones (masked policy, src/roll_out.py:27-29) or
 // all 38 (unmasked / illegal-action-penalty policy, src/roll_out.py:33-39).
 //   mode bit 0: 0 = pi.sample (inverse CDF in action order with the 24-bit uniform of `u32`), 1 = pi.mode (first max)
+// pi.sample takes the first DRAWABLE candidate whose running sum exceeds target = u * total, and the last drawable one
+// when none does.  A candidate is drawable when its own term e exceeds (target + total * 2^-18) * 2^-24:
+//   * the running sums of different lanes are fp32 sums in different associations (sequential inside a lane, the scan
+//     across lanes, the scan again for `total`), so they disagree by an ulp or two, i.e. by about 2^-24 of their height.
+//     A cell narrower than that cannot be located: without the rule a draw at the top of the range (u = 1 - 2^-24,
+//     target >= every running sum) fell through to the highest-numbered candidate whatever its probability, and a
+//     candidate with e == 0 at the head of a lane could win a draw in the middle of it;
+//   * the floor total * 2^-42 is what is left of the rule at u = 0: there every positive cell is located exactly (cum > 0
+//     holds from the first positive term on, so `cum > target` alone already rules out e == 0), and the floor keeps a
+//     call 2^18 times less likely than one draw step from being the answer to the draw 0.
+//   The mode always qualifies (e = 1), so a row with a finite candidate logit always has a drawable candidate; the chosen
+//   call has probability above 2^-24 * (u + 2^-18).  Cells at least that wide are found exactly as before.
+//   A row without one (NaN / -inf / +inf everywhere it counts) takes the mode's convention below.
 // network outputs as the GEMM wrote them: float (fmt 0), bf16 (1) or fp16 (2) -> float (exact conversions)
 __device__ __forceinline__ float net_out(const void *base, int64_t idx, int fmt) {
   if (fmt == 0) return reinterpret_cast<const float *>(base)[idx];
@@ -87,12 +100,13 @@ __device__ __forceinline__ int categorical(const void *logits, int64_t row_off, 
   int act = amax;
   if (!(mode & 1)) {
     const float target = (float)(u32 >> 8) * (1.0f / 16777216.0f) * total;  // inverse CDF, u in [0,1)
+    const float thr = (target + total * (1.0f / 262144.0f)) * (1.0f / 16777216.0f);  // narrowest cell this draw can land in
     float cum = excl;
     int first = 64, last = -1;
 #pragma unroll
     for (int i = 0; i < NI; i++) {
       cum += e[i];
-      if (ok[i]) {
+      if (ok[i] && e[i] > thr) {  // (false for a NaN term too)
         last = slot * NI + i;
         first = (first == 64 && cum > target) ? slot * NI + i : first;
       }
@@ -102,7 +116,7 @@ __device__ __forceinline__ int categorical(const void *logits, int64_t row_off, 
       first = min(first, __shfl_xor(first, off, 64));
       last = max(last, __shfl_xor(last, off, 64));
     }
-    act = (first < 64) ? first : max(last, 0);
+    act = (first < 64) ? first : ((last >= 0) ? last : amax);
   }
   // the chosen action's logit lives on slot act / NI
   const int ai = act % NI;

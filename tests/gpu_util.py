@@ -1,4 +1,6 @@
 """Helpers shared by the -m gpu parity tests: GPU State <-> oracle state comparison."""
+import os
+
 import numpy as np
 import torch
 
@@ -40,3 +42,27 @@ def random_legal_actions(rng, mask):
     m = mask.astype(np.float64)
     r = rng.random(m.shape) * m
     return r.argmax(axis=1).astype(np.int32)
+
+
+def make_env(dds, k, ws=None, lut=None, **kwargs):
+    """k: tables per wave of the per-step kernels; ws: "0" for the K-tables-per-wave fused rollout
+    (k_rollout_random<K>), "ws" for the barrier-synchronised wave-specialised kernel (k_rollout_ws) on every shape,
+    None for the library default (the flag-synchronised k_rollout_fs where it applies: substeps 1, T <= 40, n % 32 == 0;
+    k_rollout_ws otherwise); kwargs: further arguments of BridgeBidding (env_offset)."""
+    import brl_amd
+    new = {"BRL_TABLES_PER_WAVE": str(k), "BRL_ROLLOUT_WS": "0" if ws == "0" else None,
+           "BRL_ROLLOUT_FS": "0" if ws == "ws" else None}
+    old = {key: os.environ.get(key) for key in new}
+    for key, v in new.items():
+        if v is None:
+            os.environ.pop(key, None)
+        else:
+            os.environ[key] = v
+    try:
+        return brl_amd.BridgeBidding(lut=lut if lut is not None else (dds["keys"], dds["values"]), **kwargs)
+    finally:
+        for key, v in old.items():
+            if v is None:
+                os.environ.pop(key, None)
+            else:
+                os.environ[key] = v

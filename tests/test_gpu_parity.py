@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests.conftest import synthetic_lut
-from tests.gpu_util import assert_state_equal, random_legal_actions, to_np
+from tests.gpu_util import assert_state_equal, make_env, random_legal_actions, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -17,30 +17,6 @@ pytestmark = pytest.mark.gpu
 def env(dds):
     import brl_amd
     return brl_amd.BridgeBidding(lut=(dds["keys"], dds["values"]))
-
-
-def make_env(dds, k, ws=None, lut=None):
-    """k: tables per wave of the per-step kernels; ws: "0" for the K-tables-per-wave fused rollout
-    (k_rollout_random<K>), "ws" for the barrier-synchronised wave-specialised kernel (k_rollout_ws) on every shape,
-    None for the library default (the flag-synchronised k_rollout_fs where it applies: substeps 1, T <= 40, n % 32 == 0;
-    k_rollout_ws otherwise)."""
-    import brl_amd
-    new = {"BRL_TABLES_PER_WAVE": str(k), "BRL_ROLLOUT_WS": "0" if ws == "0" else None,
-           "BRL_ROLLOUT_FS": "0" if ws == "ws" else None}
-    old = {key: os.environ.get(key) for key in new}
-    for key, v in new.items():
-        if v is None:
-            os.environ.pop(key, None)
-        else:
-            os.environ[key] = v
-    try:
-        return brl_amd.BridgeBidding(lut=lut if lut is not None else (dds["keys"], dds["values"]))
-    finally:
-        for key, v in old.items():
-            if v is None:
-                os.environ.pop(key, None)
-            else:
-                os.environ[key] = v
 
 
 def test_extension_is_the_in_tree_hip_library():
