@@ -4,10 +4,13 @@ the step and its multi-rank forms."""
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
+import itertools
 
 import torch
 import torch.distributed as dist
 
+from . import _capi
 from ._capi import device_index, stream
 from ._capture import capture, capture_each, preserved, warm_up
 from .roll_out import Transition
@@ -69,6 +72,45 @@ class _DistCollectives:
         return bool(int(t.item()))
 
 
+def _gemm_group_tables(a, b, c, inner):
+    """-> the nine arrays of brl_mlp_gemm_group / brl_mlp_gemm_x3_group for the products c[i] = a[i] x b[i]: address and row
+    stride of every a, of every b, of every c, the rows and columns of every c, and the inner length they all share"""
+    n = len(c)
+    addr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
+    i64 = lambda xs: (C.c_int64 * n)(*xs)                              # noqa: E731
+    return (addr(a), i64([t.stride(0) for t in a]), addr(b), i64([t.stride(0) for t in b]), addr(c), i64([t.stride(0) for t in c]),
+            i64([t.shape[0] for t in c]), i64([t.shape[1] for t in c]), i64([inner] * n))
+
+
+def _segment_tables(parts, cols, tiles, outs):
+    """-> the (parts, cols, tiles, outs) arrays of brl_bias_finalize_ex / brl_bias_finalize_rows / brl_adam_clip_fin_gather: segment
+    i is the sum of tiles[i] partial rows of cols[i] columns at parts[i], left at outs[i]; parts / outs: tensors or addresses"""
+    n = len(parts)
+    addr = lambda xs: (C.c_void_p * n)(*[x.data_ptr() if torch.is_tensor(x) else x for x in xs])   # noqa: E731
+    return addr(parts), (C.c_int64 * n)(*cols), (C.c_int64 * n)(*tiles), addr(outs)
+
+
+def _graph_kernel_runs(program, capture_all):
+    """-> the program with every run of kernel groups replaced by ONE ("k", graph.replay): the form of a backend whose collectives
+    cannot be captured.  A collective ends a run; a wait does not (it moves in front of the run: still behind its collective, and
+    with blocking collectives it finds nothing to wait for).  ``capture_all``: a list of callables -> their graphs."""
+    out, runs, open_run = [], [], None
+    for item in program:
+        if item[0] == "c":
+            out.append(item)
+            open_run = None
+        elif item[0] == "w":
+            out.insert(len(out) - (open_run is not None), item)
+        elif open_run is None:
+            open_run = [item[1]]
+            runs.append(open_run)
+            out.append(("k", open_run))
+        else:
+            open_run.append(item[1])
+    graphs = iter(capture_all([lambda fns=fns: [fn() for fn in fns] for fns in runs]))
+    return [("k", next(graphs).replay) if item[0] == "k" else item for item in out]
+
+
 class FusedStep:
     """What every fused PPO minibatch step shares: the FLAT parameter / gradient / moment buffers the module's parameters and the
     optimizer's state become views of, the device-resident minibatch gather, the step as a PROGRAM — a list of kernel groups
@@ -78,9 +120,7 @@ class FusedStep:
     replays.  Subclasses: ``FusedMinibatch`` (the DeepMind MLPs), ``FusedFair`` (the FAIR residual net)."""
 
     def __init__(self, config, params, opt, mbs: int, device, world: int = 1, log_capacity: int = 0, collective=None):
-        from . import _capi
         self.cfg, self.params, self.opt, self.mbs, self.dev = config, params, opt, int(mbs), device
-        self.lib, self.capi = _capi.lib(), _capi
         self.world = int(world)
         # force_collectives / BRL_FORCE_DIST=1 under a process group: the multi-rank program at world 1 (tests, bench, rehearsals)
         from .dist import distributed
@@ -107,21 +147,16 @@ class FusedStep:
                 self._setup(log_capacity)
                 # warm-up and capture run real steps on the dummy batch: parameters, moments and counters are put back afterwards
                 keep.enter_context(preserved(tensors=(self.P, self.M, self.V, self.step, self.mb_index)))
-                warm_up(self._run_kernel_groups, 2, no_grad=True)   # (allocator, library heuristics)
+                kernels = [item for item in self.program if item[0] == "k"]
+                warm_up(lambda: self._run_program(kernels, False), 2, no_grad=True)   # (allocator, library heuristics)
                 torch.cuda.synchronize()
             except Exception as e:
                 err = e
             self._agree(err, "allocation / first launches")
             self._capture_all()
 
-    def _run_kernel_groups(self):
-        for item in self.program:
-            if item[0] == "k":
-                item[1]()
-
     def _setup(self, log_capacity):
         config, params, opt, device, multi = self.cfg, self.params, self.opt, self.dev, self.multi
-        _capi = self.capi
         if config.get("tuned_gemm", True):   # committed TunableOp solutions for the step's GEMM shapes (brl_amd/tuned): lookups only
             from . import tuned
             tuned.enable()
@@ -144,25 +179,11 @@ class FusedStep:
         self.P, self.G, self.M, self.V = f(n), f(n), f(n), f(n)
         self.step = torch.zeros((), dtype=torch.float32, device=device)
         self.plist = plist
-        off = 0
-        views = {}
+        self.views = {q: slice(end - k, end) for q, k, end in zip(plist, sizes, itertools.accumulate(sizes))}
         with torch.no_grad():
-            for q, k in zip(plist, sizes):
-                sl = slice(off, off + k)
-                self.P[sl].copy_(q.detach().reshape(-1))
-                st = opt.state.get(q, {})
-                if "exp_avg" in st:  # built after eager steps / from a loaded optimizer: continue from that state
-                    self.M[sl].copy_(st["exp_avg"].reshape(-1))
-                    self.V[sl].copy_(st["exp_avg_sq"].reshape(-1))
-                q.data = self.P[sl].view(q.shape)
-                q.grad = self.G[sl].view(q.shape)
-                st_step = st.get("step")
-                opt.state[q] = {"step": st_step.to(device=device, dtype=torch.float32).reshape(()) if torch.is_tensor(st_step)
-                                else torch.zeros((), dtype=torch.float32, device=device),
-                                "exp_avg": self.M[sl].view(q.shape), "exp_avg_sq": self.V[sl].view(q.shape)}
-                views[q] = sl
-                off += k
-        self.views = views
+            self._adopt()
+            for q in plist:
+                q.grad = self.G[self.views[q]].view(q.shape)
         self.x0 = f(B, 480)
         self.mask = torch.zeros((B, 38), dtype=torch.uint8, device=device)
         self.mask[:, 0] = 1  # a valid dummy batch for the warm-up iterations
@@ -228,24 +249,9 @@ class FusedStep:
                 ks = (1, self.graph_steps) if self.graph_steps > 1 else (1,)
                 graphs = capture_each([lambda k=k: self._program_steps(k) for k in ks], no_grad=True)
                 self.graph, self.graph_multi = graphs[0], (graphs[1] if len(graphs) > 1 else None)
-            else:
-                # the program with every run of kernel groups replaced by its graph (one memory pool)
-                segs = []
-                for item in self.program:
-                    if item[0] == "k":
-                        if segs and segs[-1][0] == "g":
-                            segs[-1][1].append(item[1])
-                        else:
-                            segs.append(("g", [item[1]]))
-                    elif item[0] == "c":
-                        segs.append(item)
-
-                def run(fns):
-                    for fn in fns:
-                        fn()
-                graphs = iter(capture_each([lambda fns=s[1]: run(fns) for s in segs if s[0] == "g"], pool=torch.cuda.graph_pool_handle(),
-                                           no_grad=True))
-                self.segs = [("g", next(graphs)) if s[0] == "g" else s for s in segs]
+            else:   # graphs of kernel groups (one memory pool), eager blocking collectives between their replays
+                pool = torch.cuda.graph_pool_handle()
+                self.segs = _graph_kernel_runs(self.program, lambda fns: capture_each(fns, pool=pool, no_grad=True))
         except Exception as e:
             err = e
         self._agree(err, "capture of the step")
@@ -263,17 +269,21 @@ class FusedStep:
 
     def _program_steps(self, k):
         for _ in range(k):
-            self._run_program(True)
+            self._run_program(self.program, True)
         self._drain()           # every forked stream joins before the capture ends
 
-    def _run_program(self, async_op):
-        for item in self.program:
+    def _run_program(self, program, async_op):
+        """the one interpreter of a step program.  ``async_op=False``: a collective that hands back a work object all the same is
+        waited for at once, and its "w" finds nothing"""
+        for item in program:
             if item[0] == "k":
                 item[1]()
             elif item[0] == "c":
                 w = item[2](async_op)
-                if w is not None:
+                if w is not None and async_op:
                     self._works[item[1]] = w
+                elif w is not None:
+                    w.wait()
             else:
                 w = self._works.pop(item[1], None)
                 if w is not None:
@@ -286,32 +296,35 @@ class FusedStep:
     def _bind_gather(self, fl: Transition, adv, tgt, perm, first=True):
         """binds the step's gather to a trajectory / permutation; ``first``: also gathers minibatch *mb_index now (every later
         minibatch is gathered by the Adam launch of the step before it)"""
-        import ctypes as C
-        tp = self.capi.TransitionPtrs()
-        for name in self.capi.TransitionPtrs._names:
+        tp = _capi.TransitionPtrs()
+        for name in _capi.TransitionPtrs._names:
             t = getattr(fl, name)
             setattr(tp, name, (t.view(torch.uint8) if t.dtype == torch.bool else t).data_ptr())
-        self.capi.check(self.lib.brl_mb_gather_bind(self._di(), C.byref(tp), adv.data_ptr(), tgt.data_ptr(), perm.data_ptr(),
-                                                    self.mb_index.data_ptr(), self.mbs, self.x0.data_ptr(), self.mask.data_ptr(),
-                                                    self.action.data_ptr(), self.old_v.data_ptr(), self.old_lp.data_ptr(),
-                                                    self.adv.data_ptr(), self.tgt.data_ptr(), perm.numel() // self.mbs,
-                                                    self.gargs.data_ptr(), stream()))
+        _capi.check(_capi.lib().brl_mb_gather_bind(self._di(), C.byref(tp), adv.data_ptr(), tgt.data_ptr(), perm.data_ptr(),
+                                                   self.mb_index.data_ptr(), self.mbs, self.x0.data_ptr(), self.mask.data_ptr(),
+                                                   self.action.data_ptr(), self.old_v.data_ptr(), self.old_lp.data_ptr(),
+                                                   self.adv.data_ptr(), self.tgt.data_ptr(), perm.numel() // self.mbs,
+                                                   self.gargs.data_ptr(), stream()))
         if first:
-            self.capi.check(self.lib.brl_mb_gather_dev(self._di(), self.gargs.data_ptr(), self.mbs, stream()))
+            _capi.check(_capi.lib().brl_mb_gather_dev(self._di(), self.gargs.data_ptr(), self.mbs, stream()))
 
     def _di(self):
         return device_index(self.P)
 
+    def _loss_cfg(self):
+        """-> (clip_eps, vf_coef, ent_coef, masked, value_clipping, reward_scaling) as every loss launch takes them"""
+        cfg = self.cfg
+        return (float(cfg["clip_eps"]), float(cfg["vf_coef"]), float(cfg["ent_coef"]), int(bool(cfg.get("actor_illegal_action_mask", True))),
+                int(bool(cfg.get("value_clipping", True))), int(bool(cfg.get("reward_scaling", False))))
+
     # ---- clip + Adam on rank slices (multi-rank forms) -----------------------------------------------------------------
     def _shard_norm(self, lo, hi):
-        import ctypes as C
-        self.capi.check(self.lib.brl_adam_shard_norm(self._di(), self.G.data_ptr(), C.byref(self.geom), lo, hi, 1.0 / self.world,
-                                                     self.norm_partials.data_ptr(), self.step.data_ptr(), self.mb_index.data_ptr(),
-                                                     stream()))
+        _capi.check(_capi.lib().brl_adam_shard_norm(self._di(), self.G.data_ptr(), C.byref(self.geom), lo, hi, 1.0 / self.world,
+                                                    self.norm_partials.data_ptr(), self.step.data_ptr(), self.mb_index.data_ptr(),
+                                                    stream()))
 
     def _shard_apply(self, lo, hi):
-        import ctypes as C
-        self.capi.check(self.lib.brl_adam_shard_apply(
+        _capi.check(_capi.lib().brl_adam_shard_apply(
             self._di(), self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), C.byref(self.geom), lo, hi,
             self.norm_partials.data_ptr(), self.step.data_ptr(), self.lr, self.lr_dev.data_ptr(), float(self.b1), float(self.b2),
             self.eps, self.max_norm, 1.0 / self.world, self.norm.data_ptr(), self.gargs.data_ptr(), self.mbs, stream()))
@@ -327,7 +340,7 @@ class FusedStep:
         fl, adv_c, tgt_c = self._keep
         self._steps = steps
         with torch.no_grad():
-            self._readopt()
+            self._adopt()
             allp = torch.cat(perms)
             if self.perm is None or self.perm.numel() != allp.numel():
                 self.perm = torch.empty_like(allp)
@@ -337,26 +350,25 @@ class FusedStep:
             self.lr_dev.fill_(float(self.opt.param_groups[0]["lr"]))  # constant within an update (ppo.py:186-192)
             self._bind_gather(fl, adv_c, tgt_c, self.perm)
 
-    def _readopt(self):
-        """`opt.load_state_dict` (resume) or a foreign `p.data = ...` replaces tensors that were views of the flat buffers:
-        copy their contents in and point them back at the buffers (addresses are baked into the graph)."""
+    def _adopt(self):
+        """Every parameter and its Adam state INTO the flat buffers, as views of them (addresses are baked into the graph): at
+        construction, and again at every update — `opt.load_state_dict` (resume) or a foreign `p.data = ...` replaces tensors that
+        were views.  "Replaced" is a comparison of addresses: it does not see `_version`, and a view costs nothing."""
         for q in self.plist:
-            sl = self.views[q]
-            if q.data.data_ptr() != self.P[sl].data_ptr():
-                self.P[sl].copy_(q.data.reshape(-1))
-                q.data = self.P[sl].view(q.shape)
-            st = self.opt.state.get(q)
-            if st is None or "exp_avg" not in st:
-                self.M[sl].zero_(); self.V[sl].zero_()
-                self.opt.state[q] = {"step": torch.zeros((), dtype=torch.float32, device=self.dev),
-                                     "exp_avg": self.M[sl].view(q.shape), "exp_avg_sq": self.V[sl].view(q.shape)}
-                continue
-            if st["exp_avg"].data_ptr() != self.M[sl].data_ptr():
-                self.M[sl].copy_(st["exp_avg"].reshape(-1))
-                self.V[sl].copy_(st["exp_avg_sq"].reshape(-1))
-                st["exp_avg"], st["exp_avg_sq"] = self.M[sl].view(q.shape), self.V[sl].view(q.shape)
-            if not torch.is_tensor(st["step"]) or st["step"].device != self.P.device:
-                st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=self.dev).reshape(())
+            p, m, v = (buf[self.views[q]].view(q.shape) for buf in (self.P, self.M, self.V))
+            if q.data.data_ptr() != p.data_ptr():
+                p.copy_(q.data)
+                q.data = p
+            st = self.opt.state.get(q, {})
+            if "exp_avg" not in st:                               # no Adam state (not stepped yet, or dropped): a fresh one
+                m.zero_()
+                v.zero_()
+                st = self.opt.state[q] = {"step": 0.0}
+            elif st["exp_avg"].data_ptr() != m.data_ptr():        # stepped eagerly / loaded: continue from that state
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+            st["exp_avg"], st["exp_avg_sq"] = m, v                # (already views: the same addresses again)
+            st["step"] = torch.as_tensor(st["step"], dtype=torch.float32, device=self.dev).reshape(())
 
     def run_steps(self, n: int):
         """the next n minibatch steps of the bound update"""
@@ -370,14 +382,8 @@ class FusedStep:
             for _ in range(n):
                 self.graph.replay()
             return
-        for _ in range(n):          # a backend that cannot be captured: graphs of kernel groups, eager blocking collectives between
-            for item in self.segs:
-                if item[0] == "g":
-                    item[1].replay()
-                else:
-                    w = item[2](False)
-                    if w is not None:
-                        w.wait()
+        for _ in range(n):          # a backend that cannot be captured: _graph_kernel_runs' form of the program
+            self._run_program(self.segs, False)
 
     def gather_optimizer_state(self):
         """"sharded": Adam's moments are current on this rank's slices only — before the optimizer state is SAVED, every rank
@@ -398,9 +404,9 @@ class FusedStep:
         with torch.no_grad():  # every parameter's step counter (torch keeps one per parameter)
             for q in self.plist:
                 self.opt.state[q]["step"].copy_(self.step)
-            self.capi.check(self.lib.brl_ppo_stats_rows(self._di(), self.stat_sums.data_ptr(), self.gram_sums.data_ptr(), self._steps,
-                                                        self.mbs, float(self.cfg["vf_coef"]), float(self.cfg["ent_coef"]),
-                                                        self.ill_coef, self.log.data_ptr(), stream()))
+            _capi.check(_capi.lib().brl_ppo_stats_rows(self._di(), self.stat_sums.data_ptr(), self.gram_sums.data_ptr(), self._steps,
+                                                       self.mbs, float(self.cfg["vf_coef"]), float(self.cfg["ent_coef"]),
+                                                       self.ill_coef, self.log.data_ptr(), stream()))
             self._bind_gather(*self._dummy, first=False)   # (the trajectory may be freed by the caller now)
         self._keep = None
         return self.log[:self._steps]
@@ -480,7 +486,6 @@ class FusedMinibatch(FusedStep):
         return plist, sizes, offs, lens, n
 
     def _alloc(self):
-        import ctypes as C
         params, views, f, B, config = self.params, self.views, self._f, self.mbs, self.cfg
         body = list(params.body)
         nl, H, K, hid = self.nl, self.H, self.K, self._hid
@@ -505,7 +510,7 @@ class FusedMinibatch(FusedStep):
         self.head_ksplit = max(1, min(4, H // 256))          # K ranges of the heads product (brl_ppo_heads_loss_split)
         self.head_parts = f(self.head_ksplit, B, K)
         self.vec = f(40) if self.ill_coef else None          # v1 [38], sigma_1 of the step's illegal-action matrix
-        groups = (B + 15) // 16                        # 16-row tiles of the bias-gradient column sums
+        t16, t64 = (B + 15) // 16, (B + 63) // 64      # row tiles of the bias-gradient column sums: brl_act_bwd_colsum's, brl_mlp_gemm's
         self.gram_partials = f(self.lgroups, 38 * 38)
         self.scratch = f(8192)   # single rank: norm partials (1024 blocks + the finalize blocks that ride in the norm launch)
         self.nsplit = (B + 63) // 64                   # batch splits of the head's weight / bias gradient (brl_ppo_heads_bwd)
@@ -525,27 +530,17 @@ class FusedMinibatch(FusedStep):
         # kernel's rounding: tests/test_gpu_parity.py::test_mlp_gemm_x3_beats_the_exact_kernels_error)
         self.dw_x3 = (config.get("dw_gemm") or "bf16x3") == "bf16x3" and B % 32 == 0 and H % 4 == 0 and self.x0.shape[1] % 4 == 0 and nl <= 8
         if self.dw_x3:
-            a_ = [self.dzs[l] for l in range(nl)]
-            b_ = [self.x0] + [self.hs[l] for l in range(nl - 1)]
-            c_ = [self.GW[l] for l in range(nl)]
-            i64, vp = C.c_int64 * nl, C.c_void_p * nl
-            self._gdw = (vp(*[t_.data_ptr() for t_ in a_]), i64(*[t_.stride(0) for t_ in a_]), vp(*[t_.data_ptr() for t_ in b_]),
-                         i64(*[t_.stride(0) for t_ in b_]), vp(*[t_.data_ptr() for t_ in c_]), i64(*[t_.stride(0) for t_ in c_]),
-                         i64(*[t_.shape[0] for t_ in c_]), i64(*[t_.shape[1] for t_ in c_]), i64(*([B] * nl)))
+            self._gdw = _gemm_group_tables(list(self.dzs), [self.x0] + list(self.hs[:nl - 1]), self.GW, B)
         # the head's weight-gradient role (not on the backward chain) rides with the first launch of the dz chain below the top
         self.dw_deferred = nl > 1
-        groups64 = (B + 63) // 64                      # 64-row tiles of brl_mlp_gemm's column sums
-        self.tile_rows = [64 if (self.own_gemm and l < nl - 1) else 16 for l in range(nl)]
-        self.tile_sums = [f(groups * H) for _ in body]   # per-layer partial column sums (bias gradients)
-        # one launch finishes every sum of partials: the head's weight gradient, the hidden layers' bias gradients, the head's
-        # bias gradient — in the order they sit at the end of the flat buffer
-        nseg = nl + 2
-        self._seg_scratch = (C.c_void_p * nseg)(*([self.dwh_partials.data_ptr()] + [t.data_ptr() for t in self.tile_sums]
-                                                  + [self.dbh_partials.data_ptr()]))
-        self._seg_cols = (C.c_int64 * nseg)(*([K * H] + [H] * nl + [K]))
-        self._seg_tiles = (C.c_int64 * nseg)(*([self.nsplit] + [groups64 if r == 64 else groups for r in self.tile_rows] + [self.nsplit]))
-        self._seg_db = (C.c_void_p * nseg)(*([self.GWh.data_ptr()] + [g.data_ptr() for g in self.Gb] + [self.Gbh.data_ptr()]))
-        self._nseg = nseg
+        self.tile_sums = [f(t16 * H) for _ in body]      # per-layer partial column sums (bias gradients)
+        # one launch finishes every sum of partials: the head's weight gradient, the hidden layers' bias gradients (64-row tiles
+        # where brl_mlp_gemm's epilogue left them: every layer below the top), the head's bias gradient — in the order they sit at
+        # the end of the flat buffer
+        self._nseg = nl + 2
+        self._seg = _segment_tables([self.dwh_partials] + self.tile_sums + [self.dbh_partials], [K * H] + [H] * nl + [K],
+                                    [self.nsplit] + [t64 if (self.own_gemm and l < nl - 1) else t16 for l in range(nl)] + [self.nsplit],
+                                    [self.GWh] + self.Gb + [self.Gbh])
 
     # ---- the step as a program ---------------------------------------------------------------------------------------
     def _build_program(self):
@@ -615,9 +610,9 @@ class FusedMinibatch(FusedStep):
         x = self.x0 if l == 0 else self.h[l - 1]
         W, b = self.W[l], self.b[l]
         if self.own_fwd and l > 0:                            # own kernel: bias + activation in its epilogue
-            self.capi.check(self.lib.brl_mlp_gemm(self._di(), 0, 1, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0),
-                                                  self.h[l].data_ptr(), self.h[l].stride(0), self.mbs, W.shape[0], W.shape[1], self.act,
-                                                  b.data_ptr(), None, 0, None, None, stream()))
+            _capi.check(_capi.lib().brl_mlp_gemm(self._di(), 0, 1, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0),
+                                                 self.h[l].data_ptr(), self.h[l].stride(0), self.mbs, W.shape[0], W.shape[1], self.act,
+                                                 b.data_ptr(), None, 0, None, None, stream()))
         elif self.act == 0:                                   # ReLU in the GEMM epilogue
             torch._addmm_activation(b, x, W.t(), use_gelu=False, out=self.h[l])
         else:
@@ -626,15 +621,13 @@ class FusedMinibatch(FusedStep):
     def _heads(self):
         """heads + `_loss_fn` + output gradients (two launches), backward of the merged head down to the top hidden layer's
         pre-activation (one launch)"""
-        L, chk, B = self.lib, self.capi.check, self.mbs
+        L, chk, B = _capi.lib(), _capi.check, self.mbs
         s = stream()
         di, cfg = self._di(), self.cfg
         x = self.h[self.nl - 1]
         chk(L.brl_ppo_heads_loss_split(di, x.data_ptr(), x.stride(0), self.Wh.data_ptr(), self.bh.data_ptr(), self.H,
                                        self.mask.data_ptr(), self.action.data_ptr(), self.old_v.data_ptr(), self.old_lp.data_ptr(),
-                                       self.adv.data_ptr(), self.tgt.data_ptr(), B, float(cfg["clip_eps"]), float(cfg["vf_coef"]),
-                                       float(cfg["ent_coef"]), int(bool(cfg.get("actor_illegal_action_mask", True))),
-                                       int(bool(cfg.get("value_clipping", True))), int(bool(cfg.get("reward_scaling", False))),
+                                       self.adv.data_ptr(), self.tgt.data_ptr(), B, *self._loss_cfg(),
                                        self.heads.data_ptr() if self.ill_coef else None,
                                        self.dheads.data_ptr(), self.partials.data_ptr(), self.gram_partials.data_ptr(),
                                        self.head_parts.data_ptr(), self.head_ksplit, s))
@@ -659,7 +652,7 @@ class FusedMinibatch(FusedStep):
     def _dz(self, l):
         """dz_{l-1} = (dz_l W_l) * act'(h_{l-1}) + the tile sums of db_{l-1}; the first of the chain (l = nl - 1) also hosts the head's
         dW_h / db_h partials and the step's statistics sums as extra workgroups"""
-        L, chk, B, H = self.lib, self.capi.check, self.mbs, self.H
+        L, chk, B, H = _capi.lib(), _capi.check, self.mbs, self.H
         s = stream()
         di = self._di()
         first = l == self.nl - 1 and self.dw_deferred
@@ -687,9 +680,9 @@ class FusedMinibatch(FusedStep):
         src = self.x0 if l == 0 else self.h[l - 1]
         if self.own_gemm and l > 0:
             dz, GW = self.dzs[l], self.GW[l]
-            self.capi.check(self.lib.brl_mlp_gemm(self._di(), 2, 0, dz.data_ptr(), dz.stride(0), src.data_ptr(), src.stride(0),
-                                                  GW.data_ptr(), GW.stride(0), GW.shape[0], GW.shape[1], self.mbs, self.act, None, None, 0,
-                                                  None, None, stream()))
+            _capi.check(_capi.lib().brl_mlp_gemm(self._di(), 2, 0, dz.data_ptr(), dz.stride(0), src.data_ptr(), src.stride(0),
+                                                 GW.data_ptr(), GW.stride(0), GW.shape[0], GW.shape[1], self.mbs, self.act, None, None, 0,
+                                                 None, None, stream()))
         else:
             torch.mm(self.dzs[l].t(), src, out=self.GW[l])
 
@@ -700,23 +693,22 @@ class FusedMinibatch(FusedStep):
         for l in range(nl - 1, 0, -1):
             self._dz(l)
         if self.dw_x3:
-            self.capi.check(self.lib.brl_mlp_gemm_x3_group(self._di(), 2, nl, *self._gdw, stream()))
+            _capi.check(_capi.lib().brl_mlp_gemm_x3_group(self._di(), 2, nl, *self._gdw, stream()))
             return
         if nl > 1:
             torch.bmm(self.dzs[1:].transpose(1, 2), self.hs[:nl - 1], out=self.GW_hidden)
         torch.mm(self.dzs[0].t(), self.x0, out=self.GW[0])
 
     def _seg_fin(self):
-        self.capi.check(self.lib.brl_bias_finalize_ex(self._di(), self._nseg, self._seg_scratch, self._seg_cols, self._seg_tiles,
-                                                      self._seg_db, stream()))
+        _capi.check(_capi.lib().brl_bias_finalize_ex(self._di(), self._nseg, *self._seg, stream()))
 
     def _fin_opt(self):
         """single rank: every sum of partials is finished by extra workgroups of the norm launch (brl_adam_clip_fin_gather)"""
-        self.capi.check(self.lib.brl_adam_clip_fin_gather(
+        _capi.check(_capi.lib().brl_adam_clip_fin_gather(
             self._di(), self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.n, self.step.data_ptr(), self.lr,
             self.lr_dev.data_ptr(), float(self.b1), float(self.b2), self.eps, self.max_norm, self.scratch.data_ptr(),
             self.scratch.numel(), self.mb_index.data_ptr(), self.norm.data_ptr(), self.gargs.data_ptr(), self.mbs, self._nseg,
-            self._seg_scratch, self._seg_cols, self._seg_tiles, self._seg_db, stream()))
+            *self._seg, stream()))
 
 
 
@@ -762,7 +754,6 @@ class FusedFair(FusedStep):
         return plist, sizes, ([0] if self.multi else None), ([n // self.world] if self.multi else None), n
 
     def _alloc(self):
-        import ctypes as C
         p, f, B, views = self.params, self._f, self.mbs, self.views
         L = list(p.l)
         H = self.H = L[0].weight.shape[0]
@@ -797,12 +788,9 @@ class FusedFair(FusedStep):
         self.from_gemm = (1, 3, 7, 9) if self.own_gemm else ()
         t16, t64 = (B + 15) // 16, (B + 63) // 64
         self.tiles = [f((t64 if l in self.from_gemm else t16), H) for l in range(11)]
-        self._seg_scratch = (C.c_void_p * 11)(*[t.data_ptr() for t in self.tiles])
-        self._seg_cols = (C.c_int64 * 11)(*([H] * 11))
-        self._seg_tiles = (C.c_int64 * 11)(*[t.shape[0] for t in self.tiles])
-        self._seg_db = (C.c_void_p * 11)(*[g.data_ptr() for g in self.Gb])
+        self._seg = _segment_tables(self.tiles, [H] * 11, [t.shape[0] for t in self.tiles], self.Gb)
         if not self.multi:      # single rank: the sweep through the shard launches with a one-bucket, world-1 geometry
-            g = self.capi.ShardGeom()
+            g = _capi.ShardGeom()
             g.nbuckets, g.world, g.nsub = 1, 1, 1024
             g.off[0], g.len[0] = 0, self.n
             self.geom, self.norm_partials = g, f(1024)
@@ -814,12 +802,12 @@ class FusedFair(FusedStep):
             nwg = B // 16
             assert p.critic.weight.data_ptr() == p.actor.weight.data_ptr() + 38 * H * 4 \
                 and p.critic.bias.data_ptr() == p.actor.bias.data_ptr() + 38 * 4      # the heads as one [39, H] / [39] in the flat buffer
-            sw, sb = views[p.actor.weight], views[p.critic.bias]
+            sw = views[p.actor.weight]
             self.GWh = self.G[sw.start:sw.start + 39 * H].view(39, H)
             self.gates, self.dheads = f(4, B, H), f(B, 40)
             self.ctiles = f(11 * nwg * H + nwg * 39)
             self.cpartials, self.cgram = f(nwg, 8), f(nwg, 38 * 38)
-            net, wk = self.capi.FairNet(), self.capi.FairWork()
+            net, wk = _capi.FairNet(), _capi.FairWork()
             for l, lin in enumerate(L):
                 net.w[l], net.b[l] = lin.weight.data_ptr(), lin.bias.data_ptr()
             net.head_w, net.head_b = p.actor.weight.data_ptr(), p.actor.bias.data_ptr()
@@ -829,20 +817,14 @@ class FusedFair(FusedStep):
                 setattr(wk, name, t_.data_ptr())
             self._net, self._work = net, wk
             # one launch finishes the eleven bias gradients, the heads' and this step's row of the statistics / Gram sums
-            parts = [self.ctiles.data_ptr() + 4 * l * nwg * H for l in range(12)] + [self.cpartials.data_ptr(), self.cgram.data_ptr()]
-            outs = [g_.data_ptr() for g_ in self.Gb] + [self.G[views[p.actor.bias].start:].data_ptr(), self.stat_sums.data_ptr(),
-                                                         self.gram_sums.data_ptr()]
-            cols = [H] * 11 + [39, 8, 38 * 38]
-            self._cseg = ((C.c_void_p * 14)(*parts), (C.c_int64 * 14)(*cols), (C.c_int64 * 14)(*([nwg] * 14)), (C.c_void_p * 14)(*outs))
+            self._cseg = _segment_tables([self.ctiles.data_ptr() + 4 * l * nwg * H for l in range(12)] + [self.cpartials, self.cgram],
+                                         [H] * 11 + [39, 8, 38 * 38], [nwg] * 14,
+                                         self.Gb + [self.G[views[p.actor.bias].start:], self.stat_sums, self.gram_sums])
             # the twelve weight gradients (eleven layers + the heads) dW = dz^T x as ONE launch (brl_mlp_gemm_group; else: library products)
             self.group_dw = self.own_gemm and bool(self.cfg.get("fair_group_dw", True))
-            a_ = [self.dzs[i] for i in range(nsq)] + [self.dz[6], self.dz[0], self.dheads]
-            b_ = [self.inp[i] for i in range(nsq)] + [self.cat6, self.x0, self.t["x4"]]
-            c_ = [self.GW_square[i] for i in range(nsq)] + [self.GW6, self.GW[0], self.GWh]
-            i64, vp = C.c_int64 * 12, C.c_void_p * 12
-            self._gdw = (vp(*[t_.data_ptr() for t_ in a_]), i64(*[t_.stride(0) for t_ in a_]), vp(*[t_.data_ptr() for t_ in b_]),
-                         i64(*[t_.stride(0) for t_ in b_]), vp(*[t_.data_ptr() for t_ in c_]), i64(*[t_.stride(0) for t_ in c_]),
-                         i64(*[t_.shape[0] for t_ in c_]), i64(*[t_.shape[1] for t_ in c_]), i64(*([B] * 12)))
+            self._gdw = _gemm_group_tables(list(self.dzs) + [self.dz[6], self.dz[0], self.dheads],
+                                           list(self.inp) + [self.cat6, self.x0, self.t["x4"]],
+                                           list(self.GW_square) + [self.GW6, self.GW[0], self.GWh], B)
 
     # ---- the step ------------------------------------------------------------------------------------------------------
     def _build_program(self):
@@ -876,17 +858,17 @@ class FusedFair(FusedStep):
         """dz_l *= act'(gate) in place (gate = the activation's OUTPUT; self.unit_gate: no activation) + its column sums per
         16-row tile = the partials of db_l"""
         dz = self.dz[l]
-        self.capi.check(self.lib.brl_act_bwd_colsum(self._di(), dz.data_ptr(), gate.data_ptr(), self.mbs, self.H, dz.stride(0), self.act,
-                                                    self.tiles[l].data_ptr(), stream()))
+        _capi.check(_capi.lib().brl_act_bwd_colsum(self._di(), dz.data_ptr(), gate.data_ptr(), self.mbs, self.H, dz.stride(0), self.act,
+                                                   self.tiles[l].data_ptr(), stream()))
 
     def _dx(self, l, gate, out, bias_of=None):
         """out = (dz_l W_l) * act'(gate); bias_of = k: `out` IS dz_k and the launch leaves db_k's partials (brl_mlp_gemm, GATE_COLSUM)"""
         dz, W = self.dz[l], self.W[l]
         if self.own_gemm:
             cs = self.tiles[bias_of] if bias_of is not None else None
-            self.capi.check(self.lib.brl_mlp_gemm(self._di(), 1, 2, dz.data_ptr(), dz.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(),
-                                                  out.stride(0), self.mbs, W.shape[1], W.shape[0], self.act, None, gate.data_ptr(),
-                                                  gate.stride(0), cs.data_ptr() if cs is not None else None, None, stream()))
+            _capi.check(_capi.lib().brl_mlp_gemm(self._di(), 1, 2, dz.data_ptr(), dz.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(),
+                                                 out.stride(0), self.mbs, W.shape[1], W.shape[0], self.act, None, gate.data_ptr(),
+                                                 gate.stride(0), cs.data_ptr() if cs is not None else None, None, stream()))
             return
         torch.mm(dz, W, out=out)
         if bias_of is not None:
@@ -899,13 +881,10 @@ class FusedFair(FusedStep):
     def _grads_chain(self):
         """the same through brl_fair_chain: one launch for forward, loss and the backward chain, the weight gradients as four
         products, one launch for every bias gradient and the step's statistics row"""
-        cfg, B = self.cfg, self.mbs
-        s = stream()
-        chk, L, di = self.capi.check, self.lib, self._di()
+        B, s = self.mbs, stream()
+        chk, L, di = _capi.check, _capi.lib(), self._di()
         chk(L.brl_fair_chain(di, self._net, self.x0.data_ptr(), self.mask.data_ptr(), self.action.data_ptr(), self.old_v.data_ptr(),
-                             self.old_lp.data_ptr(), self.adv.data_ptr(), self.tgt.data_ptr(), B, float(cfg["clip_eps"]),
-                             float(cfg["vf_coef"]), float(cfg["ent_coef"]), int(bool(cfg.get("actor_illegal_action_mask", True))),
-                             int(bool(cfg.get("value_clipping", True))), int(bool(cfg.get("reward_scaling", False))), self.act,
+                             self.old_lp.data_ptr(), self.adv.data_ptr(), self.tgt.data_ptr(), B, *self._loss_cfg(), self.act,
                              self._work, s))
         if self.group_dw:
             chk(L.brl_mlp_gemm_group(di, 2, 12, *self._gdw, s))
@@ -951,12 +930,11 @@ class FusedFair(FusedStep):
         if cfg.get("reward_scaling", False):                   # src/update.py:31-44 (jnp std: ddof = 0)
             adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
         s = stream()
-        chk, L, di = self.capi.check, self.lib, self._di()
+        chk, L, di = _capi.check, _capi.lib(), self._di()
         chk(L.brl_ppo_loss(di, self.logits.data_ptr(), 38, self.value.data_ptr(), self.mask.data_ptr(), self.action.data_ptr(),
-                           self.old_v.data_ptr(), self.old_lp.data_ptr(), adv.data_ptr(), self.tgt.data_ptr(), B, float(cfg["clip_eps"]),
-                           float(cfg["vf_coef"]), float(cfg["ent_coef"]), int(bool(cfg.get("actor_illegal_action_mask", True))),
-                           int(bool(cfg.get("value_clipping", True))), self.dlogits.data_ptr(), self.dvalue.data_ptr(),
-                           self.partials.data_ptr(), self.illp.data_ptr(), s))
+                           self.old_v.data_ptr(), self.old_lp.data_ptr(), adv.data_ptr(), self.tgt.data_ptr(), B,
+                           *self._loss_cfg()[:5],                  # (no reward_scaling: adv is normalised above)
+                           self.dlogits.data_ptr(), self.dvalue.data_ptr(), self.partials.data_ptr(), self.illp.data_ptr(), s))
         row = self.mb_index.to(torch.int64)
         self.stat_sums.index_copy_(0, row, torch.mm(self.ones_row[:, :self.lgroups], self.partials))
         gram = torch.mm(self.illp.t(), self.illp)
@@ -1005,4 +983,4 @@ class FusedFair(FusedStep):
         torch.bmm(self.dzs.transpose(1, 2), self.inp, out=self.GW_square)
         torch.mm(dz[6].t(), self.cat6, out=self.GW6)
         torch.mm(dz[0].t(), x0, out=self.GW[0])
-        chk(L.brl_bias_finalize_ex(di, 11, self._seg_scratch, self._seg_cols, self._seg_tiles, self._seg_db, s))
+        chk(L.brl_bias_finalize_ex(di, 11, *self._seg, s))

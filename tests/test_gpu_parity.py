@@ -2351,6 +2351,86 @@ def test_fused_update_follows_a_reloaded_optimizer_state():
     assert {int(st["step"]) for st in rs[1]["opt"].state.values()} == {8}
 
 
+@pytest.mark.parametrize("case", ["replaced_data", "dropped_state", "float_step"])
+@pytest.mark.parametrize("model,mbs", [("DeepMind", 64), ("FAIR", 16)])
+def test_fused_update_adopts_foreign_parameters_and_state(model, mbs, case):
+    """Between two updates somebody (a) replaces a hidden weight's `.data` with a fresh tensor of other values, (b) deletes one
+    parameter's entry of `opt.state`, (c) sets the first parameter's `state["step"]` to a Python float: after the next
+    `begin_update` every parameter and moment is a view of the flat buffers again (addresses are baked into the graph), P holds the
+    replaced values, the dropped moments are zero, the step count is an fp32 tensor on the device — and the update then matches an
+    eager torch.optim.Adam + clip_grad_norm_ run from the same state, to test_fused_update_follows_a_reloaded_optimizer_state's
+    tolerances.  "The same state": the fused step keeps ONE step counter — the first parameter's (torch keeps one per parameter) —
+    so the eager run starts every parameter at that count, with zero moments where they were dropped.  Minibatch 64 = one full
+    64-row column-sum tile and one split of the head's backward; minibatch 16 = one brl_fair_chain workgroup; two minibatch steps
+    per update: the second minibatch is gathered inside the step."""
+    from brl_amd.models import make_forward_pass
+    from brl_amd.update import FusedFair, FusedMinibatch, make_optimizer, make_update_step
+    from tests.test_update_cpu import CFG, fake_batch
+    fp = make_forward_pass("relu", model)
+    cfg = dict(CFG, minibatch_size=mbs, update_epochs=1)
+    upd = make_update_step(cfg, fp)
+    data = []
+    for seed in (31, 32):
+        tb, adv, tgt = fake_batch(4, mbs // 2, seed=seed)          # 2 * mbs rows
+        data.append((type(tb)(*[x.cuda() for x in tb]), adv.cuda(), tgt.cuda()))
+    net = fp.init(3, device="cuda")
+    rs, _ = upd((net, None, None, None, 0, 5), *data[0])
+    fm, opt = rs[1]["graphed"], rs[1]["opt"]
+    assert isinstance(fm, FusedMinibatch if model == "DeepMind" else FusedFair), rs[1].get("graph_error")
+    assert model == "DeepMind" or fm.chain
+    hidden = (net.body[2] if model == "DeepMind" else net.l[3])
+    count = 2.0
+    if case == "replaced_data":
+        fresh = torch.randn(hidden.weight.shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)) * 0.05
+        hidden.weight.data = fresh.clone()
+    elif case == "dropped_state":
+        del opt.state[hidden.bias]
+    else:
+        count = 7.0
+        opt.state[fm.plist[0]]["step"] = count
+    # ---- the eager run's start: the same weights, the same moments (zeros where dropped), the fused step's one count
+    ref = fp.init(3, device="cuda")
+    ref.load_state_dict({k: v.detach().clone() for k, v in net.state_dict().items()})
+    cfg_e = dict(cfg, graph_update=False, fused_update=False)
+    opt_e = make_optimizer(cfg_e, ref)
+    for q, q_e in zip(net.parameters(), ref.parameters()):
+        st = opt.state.get(q, {})
+        opt_e["opt"].state[q_e] = {"step": torch.tensor(count, device="cuda"),
+                                   "exp_avg": st["exp_avg"].clone() if "exp_avg" in st else torch.zeros_like(q_e),
+                                   "exp_avg_sq": st["exp_avg_sq"].clone() if "exp_avg" in st else torch.zeros_like(q_e)}
+    checked = []
+
+    def begin_update_checked(*args):
+        type(fm).begin_update(fm, *args)
+        for q in fm.plist:
+            sl, st = fm.views[q], opt.state[q]
+            assert q.data.data_ptr() == fm.P[sl].data_ptr() and q.shape == st["exp_avg"].shape == st["exp_avg_sq"].shape
+            assert st["exp_avg"].data_ptr() == fm.M[sl].data_ptr() and st["exp_avg_sq"].data_ptr() == fm.V[sl].data_ptr()
+            assert q.grad.data_ptr() == fm.G[sl].data_ptr()
+            assert st["step"].dtype == torch.float32 and st["step"].device == fm.P.device and st["step"].shape == ()
+        if case == "replaced_data":
+            assert torch.equal(fm.P[fm.views[hidden.weight]].view(fresh.shape), fresh)
+        elif case == "dropped_state":
+            sl = fm.views[hidden.bias]
+            assert not fm.M[sl].any() and not fm.V[sl].any() and float(opt.state[hidden.bias]["step"]) == 0.0
+        else:
+            assert float(opt.state[fm.plist[0]]["step"]) == count
+        assert float(fm.step) == count
+        checked.append(True)
+
+    fm.begin_update = begin_update_checked
+    rs, _ = upd(rs, *data[1])
+    assert checked == [True] and rs[1]["graphed"] is fm
+    make_update_step(cfg_e, fp)((ref, opt_e, None, None, 0, 6), *data[1])     # (the same rng: the same permutation)
+    got = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+    want = torch.cat([p.detach().reshape(-1) for p in ref.parameters()])
+    d = (got - want).abs()
+    print(f"{model} {case}: max |fused - eager| = {float(d.max()):.3e}, mean = {float(d.mean()):.3e}, largest "
+          f"excess over atol 1e-7 + rtol 1e-6 = {float((d - 1e-7 - 1e-6 * want.abs()).max()):.3e}")
+    assert torch.allclose(got, want, atol=1e-7, rtol=1e-6), float(d.max())
+    assert {int(st["step"]) for st in opt.state.values()} == {int(count) + 2}
+
+
 def test_fused_update_helpers_match_torch():
     """brl_act_bwd_colsum + brl_bias_finalize_ex, brl_adam_clip_fin_gather and brl_mb_gather_bind / _dev against their torch counterparts."""
     import ctypes as C

@@ -431,3 +431,89 @@ def test_adam_step_matches_torch_adam_in_float64(clipping, max_norm):
         assert np.abs(flat(Pn) - np.concatenate([q.detach().numpy().reshape(-1) for q in tp])).max() < 1e-15 * 10
         assert np.abs(flat(Mn) - np.concatenate([opt.state[q]["exp_avg"].numpy().reshape(-1) for q in tp])).max() < 1e-15
         assert np.abs(flat(Vn) - np.concatenate([opt.state[q]["exp_avg_sq"].numpy().reshape(-1) for q in tp])).max() < 1e-15
+
+
+def test_fused_step_program_has_one_runner_for_both_strategies():
+    """brl_amd.fused_update: the step program of kernel groups ("k"), collectives ("c") and waits ("w") has ONE interpreter.  The
+    form of a backend that cannot be captured (every run of kernel groups = one graph, blocking collectives between the replays)
+    calls the same stubs in the same order as the captured form; a blocking collective that hands back a work object all the same
+    is waited for exactly once, at once; nothing is left in `_works`."""
+    from brl_amd.fused_update import FusedStep, _graph_kernel_runs
+    calls, works = [], []
+
+    class Work:
+        def __init__(self, key):
+            self.key, self.waits = key, 0
+
+        def wait(self):
+            self.waits += 1
+            calls.append(("wait", self.key))
+
+    def k(name):
+        return ("k", lambda: calls.append(("k", name)))
+
+    def c(key):
+        def issue(async_op):
+            calls.append(("c", key))
+            works.append(Work(key))
+            return works[-1]
+        return ("c", key, issue)
+
+    # (the shape of the sharded program: parameters gathered by the step before, gradients reduced bucket by bucket)
+    program = [("w", "ag1"), k("fwd0"), ("w", "ag0"), k("fwd1"), k("heads"), k("dw1"), c("rs0"), k("dz1"), k("dw0"), c("rs1"),
+               ("w", "rs0"), ("w", "rs1"), k("norm"), c("agn"), ("w", "agn"), k("adam"), c("ag1"), c("ag0")]
+    launches = lambda: [x for x in calls if x[0] != "wait"]   # noqa: E731
+    fs = FusedStep.__new__(FusedStep)
+    fs._works = {}
+    for _ in range(2):
+        fs._run_program(program, True)
+    fs._drain()
+    captured = launches()
+    assert captured == 2 * [("k", "fwd0"), ("k", "fwd1"), ("k", "heads"), ("k", "dw1"), ("c", "rs0"), ("k", "dz1"), ("k", "dw0"), ("c", "rs1"),
+                            ("k", "norm"), ("c", "agn"), ("k", "adam"), ("c", "ag1"), ("c", "ag0")]
+    assert [w.waits for w in works] == [1] * 10 and fs._works == {}
+    assert calls.index(("wait", "ag1")) > calls.index(("c", "ag0"))        # (waited for by the NEXT step, not at once)
+
+    class Graph:                             # stands for a captured run of kernel groups
+        def __init__(self, fn):
+            self.replay = fn
+
+    eager = _graph_kernel_runs(program, lambda fns: [Graph(fn) for fn in fns])
+    assert [item[0] for item in eager] == ["w", "w", "k", "c", "k", "c", "w", "w", "k", "c", "w", "k", "c", "c"]
+    assert [item[1] for item in eager if item[0] != "k"] == ["ag1", "ag0", "rs0", "rs1", "rs0", "rs1", "agn", "agn", "ag1", "ag0"]
+    del calls[:], works[:]
+    for _ in range(2):
+        fs._run_program(eager, False)
+        assert fs._works == {}
+    assert launches() == captured
+    assert [w.waits for w in works] == [1] * 10
+    for i, x in enumerate(calls):
+        if x[0] == "c":
+            assert calls[i + 1] == ("wait", x[1])
+    # the kernel groups alone (the constructor's first launches): the same runner over the "k" items
+    del calls[:]
+    fs._run_program([item for item in program if item[0] == "k"], False)
+    assert calls == [x for x in captured[:13] if x[0] == "k"]
+
+
+def test_fused_step_table_builders_hold_addresses_strides_and_shapes():
+    """brl_amd.fused_update._gemm_group_tables: the nine arrays of a grouped weight-gradient launch, element for element, from
+    views with row strides of their own; _segment_tables: tensors and raw addresses mixed"""
+    from brl_amd.fused_update import _gemm_group_tables, _segment_tables
+    x, y, z = torch.zeros(5, 7), torch.zeros(6, 9), torch.zeros(4, 10)
+    w = torch.zeros(3, 2, 5)
+    a = [x[:, :3], y[1:, 2:6]]               # [5, 3] rows 7 apart; [5, 4] rows 9 apart, 9 + 2 floats into y
+    b = [z[:, 4:], w[1]]                     # [4, 6] rows 10 apart, 4 floats into z; [2, 5] contiguous, 10 floats into w
+    c = [y[:3, :6], w[2].t()[:, :1]]         # [3, 6] rows 9 apart; [5, 1]: rows 1 apart, 20 floats into w
+    t = _gemm_group_tables(a, b, c, 5)
+    assert len(t) == 9 and all(len(arr) == 2 for arr in t)
+    assert [list(arr) for arr in t] == [[x.data_ptr(), y.data_ptr() + 4 * 11], [7, 9],
+                                        [z.data_ptr() + 4 * 4, w.data_ptr() + 4 * 10], [10, 5],
+                                        [y.data_ptr(), w.data_ptr() + 4 * 20], [9, 1],
+                                        [3, 5], [6, 1], [5, 5]]
+    import ctypes
+    assert [arr._type_ for arr in t] == [ctypes.c_void_p, ctypes.c_int64] * 3 + [ctypes.c_int64] * 3
+    parts, cols, tiles, outs = _segment_tables([x, y.data_ptr() + 8, z[2:]], [7, 9, 10], [5, 6, 2], [w.data_ptr(), w[1], w.data_ptr() + 80])
+    assert list(parts) == [x.data_ptr(), y.data_ptr() + 8, z.data_ptr() + 4 * 20] and list(cols) == [7, 9, 10]
+    assert list(tiles) == [5, 6, 2] and list(outs) == [w.data_ptr(), w.data_ptr() + 40, w.data_ptr() + 80]
+    assert [arr._type_ for arr in (parts, cols, tiles, outs)] == [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
