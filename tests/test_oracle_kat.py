@@ -58,7 +58,7 @@ def test_score_extremes(oracle):
                for (x, xx) in ((0, 0), (1, 0), (1, 1)) for t in range(14)) == 7600
 
 
-@pytest.mark.parametrize("args,want", [
+KNOWN_CONTRACTS = [
     # (strain C,D,H,S,NT; level; vul; X; XX; tricks) -> score; laws of duplicate bridge
     ((4, 3, 0, 0, 0, 9), 400), ((4, 3, 1, 0, 0, 9), 600), ((3, 4, 0, 0, 0, 10), 420), ((2, 4, 1, 0, 0, 10), 620),
     ((0, 5, 0, 0, 0, 11), 400), ((1, 5, 1, 0, 0, 11), 600), ((4, 6, 0, 0, 0, 12), 990), ((4, 6, 1, 0, 0, 12), 1440),
@@ -70,7 +70,10 @@ def test_score_extremes(oracle):
     ((4, 3, 0, 0, 0, 8), -50), ((4, 3, 1, 0, 0, 6), -300), ((4, 3, 0, 1, 0, 8), -100), ((4, 3, 0, 1, 0, 7), -300),
     ((4, 3, 0, 1, 0, 6), -500), ((4, 3, 0, 1, 0, 5), -800), ((4, 3, 1, 1, 0, 8), -200), ((4, 3, 1, 1, 0, 7), -500),
     ((4, 3, 1, 1, 0, 6), -800), ((4, 3, 1, 1, 1, 8), -400), ((4, 3, 0, 1, 1, 5), -1600), ((4, 3, 1, 1, 1, 5), -2200),
-])
+]
+
+
+@pytest.mark.parametrize("args,want", KNOWN_CONTRACTS)
 def test_score_known_contracts(oracle, args, want):
     assert oracle.score(*args) == want
 
