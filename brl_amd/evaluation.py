@@ -460,6 +460,60 @@ def make_simple_duplicate_evaluate(eval_env: BridgeBidding, team1_activation, te
     return duplicate_evaluate
 
 
+def eval_counts(env: BridgeBidding, n: int, tables, bid_count, packed) -> torch.Tensor:
+    """The ``brl_eval_reduce`` launch: the int64 counters (layout: above k_eval_reduce, brl_amd/csrc/brl_eval.hip) of the finished
+    ``tables`` — (table A, table B) or (the one table,) —, of ``bid_count`` [n, 2, 35] and of the step counts in ``packed``
+    (either may be None: its counters stay 0)."""
+    counts = torch.empty(_capi.EVAL_COUNTS, dtype=torch.int64, device=env.device)
+    pa = tables[0]._ptrs()
+    pb = tables[1]._ptrs() if len(tables) > 1 else None
+    check(_capi.lib().brl_eval_reduce(env._h, n, C.byref(pa), C.byref(pb) if pb is not None else None,
+                                      ptr(bid_count), ptr(packed), ptr(counts), stream()))
+    return counts
+
+
+def eval_log_info(c: torch.Tensor, stats, cum_return: torch.Tensor, dup: bool, sh: _Shard):
+    """``log_info`` of ``make_evaluate`` (src/evaluation.py:985-1031 duplicate: 23 entries; :583-605 single table: 19) from the
+    counters of ``eval_counts`` summed over the ranks, as float64 (``c``), the step log (``stats``: illegal_prob_sum, step_count,
+    pass_count) and ``cum_return``.  Plain torch on whatever device the tensors live on."""
+    fn = float(sh.n_global)
+    steps = stats.step_count.to(torch.float32)
+    if sh.active:   # per-board ratios are averaged over all boards: all-reduce their sums
+        ratio = sh.allsum(torch.cat([(stats.illegal_prob_sum / steps).to(torch.float64).sum(dim=0),
+                                     (stats.pass_count.to(torch.float32) / steps).to(torch.float64).sum(dim=0)]))
+        illegal, passes = (ratio[:2] / fn).to(torch.float32), (ratio[2:] / fn).to(torch.float32)
+        x = cum_return.to(torch.float64)
+        cr = sh.allsum(torch.stack([x.sum(), (x * x).sum()]))
+        cr_mean = cr[0] / fn
+        cr_se = (((cr[1] - fn * cr_mean * cr_mean) / (fn - 1.0)).clamp_min(0.0).sqrt() / (fn ** 0.5)).to(torch.float32)
+        cr_mean = cr_mean.to(torch.float32)
+    else:
+        illegal = (stats.illegal_prob_sum / steps).mean(dim=0)          # :857-862 (x / y per board, then mean)
+        passes = (stats.pass_count.to(torch.float32) / steps).mean(dim=0)  # :1029-1030
+        cr_mean = cum_return.mean()
+        cr_se = cum_return.std(unbiased=True) / (fn ** 0.5) if dup else None   # :984
+    ntab = 2.0 if dup else 1.0
+
+    def both(i):  # (table A + table B) / 2 of a per-table ratio count / n  (:985-1028)
+        return ((c[i] + (c[80 + i] if dup else 0.0)) / fn / ntab).to(torch.float32)
+
+    def both_vec(i):
+        return ((c[i:i + 35] + (c[80 + i:80 + i + 35] if dup else 0.0)) / fn / ntab).to(torch.float32)
+
+    bid_div = 2.0 if dup else 1.0                                    # :992-993 actor_bid.mean(axis=0) / 2
+    actor_bid = (c[160:195] / fn / bid_div).to(torch.float32)
+    opp_bid = (c[195:230] / fn / bid_div).to(torch.float32)
+    step_count_mean = (c[230] / fn).to(torch.float32)                # state._step_count.mean()
+    common = (illegal[0], illegal[1], step_count_mean, actor_bid, opp_bid, both_vec(10), both_vec(45),
+              (c[10:45].sum() + (c[90:125].sum() if dup else 0.0)).div(fn * ntab).to(torch.float32),  # declarer ratios
+              (c[45:80].sum() + (c[125:160].sum() if dup else 0.0)).div(fn * ntab).to(torch.float32),
+              both(1), both(2), both(3), both(4), both(5), both(6), both(7), both(8), both(0))
+    if dup:
+        score = ((c[9] / fn + c[89] / fn) / 2).to(torch.float32)      # :988
+        return (cr_mean, cr_se, score) + common + (passes[0], passes[1])
+    return (cr_mean,) + common
+
+
 def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, team2_activation, team2_model_type,
                   team2_params, num_eval_envs, game_mode="competitive", duplicate=False, sync_every: int = 16,
                   record_actions=None, record_logits=None, shard=None):
@@ -503,50 +557,13 @@ def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, t
             if not dup:  # make_terminated_log on the final state (:463-487): one "table" built from it
                 f = State(eval_env, state.packed)
                 tables = (Table_info(f.terminated, rewards_sum, f._last_bid, f._last_bidder, f._call_x, f._call_xx),)
-            counts = torch.empty(_capi.EVAL_COUNTS, dtype=torch.int64, device=dev)
-            pa = tables[0]._ptrs()
-            pb = tables[1]._ptrs() if dup else None
-            check(_capi.lib().brl_eval_reduce(eval_env._h, n, C.byref(pa), C.byref(pb) if pb is not None else None,
-                                              ptr(stats.bid_count), ptr(state.packed), ptr(counts), stream()))
-            c = sh.allsum(counts).to(torch.float64)   # (exact integer counts: the histograms of all ranks' boards)
-            fn = float(sh.n_global)
-            steps = stats.step_count.to(torch.float32)
-            if sh.active:   # per-board ratios are averaged over all boards: all-reduce their sums
-                ratio = sh.allsum(torch.cat([(stats.illegal_prob_sum / steps).to(torch.float64).sum(dim=0),
-                                             (stats.pass_count.to(torch.float32) / steps).to(torch.float64).sum(dim=0)]))
-                illegal, passes = (ratio[:2] / fn).to(torch.float32), (ratio[2:] / fn).to(torch.float32)
-                x = cum_return.to(torch.float64)
-                cr = sh.allsum(torch.stack([x.sum(), (x * x).sum()]))
-                cr_mean = cr[0] / fn
-                cr_se = (((cr[1] - fn * cr_mean * cr_mean) / (fn - 1.0)).clamp_min(0.0).sqrt() / (fn ** 0.5)).to(torch.float32)
-                cr_mean = cr_mean.to(torch.float32)
-            else:
-                illegal = (stats.illegal_prob_sum / steps).mean(dim=0)          # :857-862 (x / y per board, then mean)
-                passes = (stats.pass_count.to(torch.float32) / steps).mean(dim=0)  # :1029-1030
-                cr_mean = cum_return.mean()
-                cr_se = cum_return.std(unbiased=True) / (fn ** 0.5) if dup else None   # :984
-            ntab = 2.0 if dup else 1.0
-
-            def both(i):  # (table A + table B) / 2 of a per-table ratio count / n  (:985-1028)
-                return ((c[i] + (c[80 + i] if dup else 0.0)) / fn / ntab).to(torch.float32)
-
-            def both_vec(i):
-                return ((c[i:i + 35] + (c[80 + i:80 + i + 35] if dup else 0.0)) / fn / ntab).to(torch.float32)
-
-            bid_div = 2.0 if dup else 1.0                                    # :992-993 actor_bid.mean(axis=0) / 2
-            actor_bid = (c[160:195] / fn / bid_div).to(torch.float32)
-            opp_bid = (c[195:230] / fn / bid_div).to(torch.float32)
-            step_count_mean = (c[230] / fn).to(torch.float32)                # state._step_count.mean()
-            common = (illegal[0], illegal[1], step_count_mean, actor_bid, opp_bid, both_vec(10), both_vec(45),
-                      (c[10:45].sum() + (c[90:125].sum() if dup else 0.0)).div(fn * ntab).to(torch.float32),  # declarer ratios
-                      (c[45:80].sum() + (c[125:160].sum() if dup else 0.0)).div(fn * ntab).to(torch.float32),
-                      both(1), both(2), both(3), both(4), both(5), both(6), both(7), both(8), both(0))
+            # (exact integer counts: the histograms of all ranks' boards)
+            c = sh.allsum(eval_counts(eval_env, n, tables, stats.bid_count, state.packed)).to(torch.float64)
+            log_info = eval_log_info(c, stats, cum_return, dup, sh)
             if dup:
-                score = ((c[9] / fn + c[89] / fn) / 2).to(torch.float32)      # :988
-                log_info = (cr_mean, cr_se, score) + common + (passes[0], passes[1])
                 return log_info, tables[0], tables[1]
             final = State(eval_env, state.packed).replace(rewards=rewards_sum)  # :582
-            return final, (cr_mean,) + common
+            return final, log_info
 
     def duplicate_evaluate(actor_params, rng_key):
         return run(actor_params, rng_key, True)

@@ -37,6 +37,14 @@ def assert_state_equal(gpu_state, orc_state, fields=None, where=""):
             raise AssertionError(f"{where}: field {of} differs on {len(bad)} tables, first table {e}:\n gpu={g[e]}\n orc={o[e]}")
 
 
+def _assert_log_info(got, want, names=None):
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        g, w = to_np(g).astype(np.float64), np.asarray(w, np.float64)
+        # counts / n in fp32 on both sides, sums of <= 8192 terms: 1e-6 absolute + 1e-5 relative
+        assert g.shape == w.shape and np.allclose(g, w, rtol=1e-5, atol=1e-6), f"log_info[{i}]: {g} != {w}"
+
+
 def random_legal_actions(rng, mask):
     """one uniformly random legal action per row of a [N,38] 0/1 mask"""
     m = mask.astype(np.float64)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests.conftest import synthetic_lut
-from tests.gpu_util import assert_state_equal, make_env, random_legal_actions, to_np
+from tests.gpu_util import _assert_log_info, assert_state_equal, make_env, random_legal_actions, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -1171,14 +1171,6 @@ def _replay_evaluate(oracle, rec_actions, rec_logits, seed, n, duplicate):
         cum += ref["rewards"][:, 0]
     assert ref["terminated"].all()
     return ref, oA, oB, cum, rsum, log
-
-
-def _assert_log_info(got, want, names=None):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        g, w = to_np(g).astype(np.float64), np.asarray(w, np.float64)
-        # counts / n in fp32 on both sides, sums of <= 8192 terms: 1e-6 absolute + 1e-5 relative
-        assert g.shape == w.shape and np.allclose(g, w, rtol=1e-5, atol=1e-6), f"log_info[{i}]: {g} != {w}"
 
 
 @pytest.mark.parametrize("n,game_mode", [(640, "competitive"), (2048, "competitive"), (300, "free-run")])
