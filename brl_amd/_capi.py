@@ -163,6 +163,7 @@ def lib() -> C.CDLL:
     sigs.update(league_signatures())
     sigs.update(boards_signatures())
     sigs.update(book_argtypes())
+    sigs.update(par_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -220,6 +221,15 @@ def book_argtypes() -> dict:
     return {
         "brl_book_samples": [i32, _vp, i64, _vp, i32, i32, _vp, _vp, _vp],
         "brl_book_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp],
+    }
+
+
+def par_argtypes() -> dict:
+    """argtypes of include/brl_par.h (the double-dummy par; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_par": [i32, _vp, _vp, _vp, i64, _vp, _vp],
+        "brl_par_imp": [i32, _vp, _vp, i64, i32, _vp, _vp],
     }
 
 

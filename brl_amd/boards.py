@@ -274,11 +274,13 @@ class BoardRecords:
     (``RECORD_DTYPE``); ``imp`` int32 [n] (pair sitting North-South at table A); ``dda`` uint8 [n,20]; ``board_id`` int64 [n];
     ``cum_return`` float32 [n]: the evaluator's own per-board return (player 0's IMP), as ``board_match`` accumulated it.
     Everything named is read from ``cpu()``'s arrays, which are copied from the device once and refuse a record whose self-check
-    bit is clear."""
+    bit is clear.  ``par``: the boards' par records when they are known already (``par.PAR_DTYPE`` [n], or their bytes);
+    otherwise ``par()`` computes them from ``dda`` on first use."""
 
-    def __init__(self, table_a, table_b=None, imp=None, dda=None, board_id=None, cum_return=None):
+    def __init__(self, table_a, table_b=None, imp=None, dda=None, board_id=None, cum_return=None, par=None):
         self.table_a, self.table_b, self.imp, self.dda, self.board_id = table_a, table_b, imp, dda, board_id
         self.cum_return = cum_return
+        self._par = par
         self._host = {}
 
     def __len__(self):
@@ -316,19 +318,64 @@ class BoardRecords:
     def hands(self, i, table="a") -> str:
         return pbn_deal(self.cpu(table)[i]["hands"])
 
-    def _table_dict(self, i, table):
+    def _table_dict(self, i, table, par=False):
         r = self.cpu(table)[i]
         has = bool(r["flags"] & TERMINATED) and not r["flags"] & (PASSED_OUT | ILLEGAL)
-        return {"auction": self.auction(i, table), "contract": self.contract(i, table),
-                "declarer": SEATS[r["declarer"]] if has else None, "tricks": int(r["tricks"]) if has else None,
-                "score_ns": int(r["score_ns"])}
+        out = {"auction": self.auction(i, table), "contract": self.contract(i, table),
+               "declarer": SEATS[r["declarer"]] if has else None, "tricks": int(r["tricks"]) if has else None,
+               "score_ns": int(r["score_ns"])}
+        if par:
+            from .par import NO_RESULT
+            v = int(self.imp_vs_par(table)[i])
+            out["imp_vs_par"] = None if v == NO_RESULT else v
+        return out
 
-    def boards(self):
-        """one dict per board: the dataset's fields plus ``table_a`` / ``table_b`` and ``imp``"""
-        a = self.cpu("a")
-        dda, ids, imp = self._np("dda"), self._np("board_id"), self._np("imp")
+    def _dda(self):
+        dda = self._np("dda")
         if dda is None:
             raise ValueError("the deals' double-dummy tables (dda=) are needed to write boards")
+        return dda
+
+    def par(self) -> np.ndarray:
+        """the boards' par records (``par.PAR_DTYPE`` [n]; include/brl_par.h): one ``brl_par`` launch on first use, from
+        ``dda`` and table A's dealer and vulnerability"""
+        if "par" not in self._host:
+            from . import par as P
+            if self._par is None:
+                self._dda()
+                a = self.table_a
+                if isinstance(a, np.ndarray):
+                    a = self.cpu("a")
+                    self._par = P.par_of(self.dda, a["dealer"], a["vul_ns"], a["vul_ew"])
+                else:
+                    at = lambda name: a[:, RECORD_DTYPE.fields[name][1]]   # noqa: E731  (the byte columns of the records)
+                    self._par = P.par_of(self.dda, at("dealer"), at("vul_ns"), at("vul_ew"))
+            self._host["par"] = P.par_array(self._par)
+        return self._host["par"]
+
+    def imp_vs_par(self, table="a") -> np.ndarray:
+        """int32 [n]: the IMP of the table's North-South score against par; ``par.NO_RESULT`` where the table has no result.
+        Records on the device go through ``brl_par_imp``, host arrays through the same arithmetic in numpy."""
+        key = "imp_vs_par_" + table
+        if key not in self._host:
+            from . import par as P
+            par = self.par()
+            src = {"a": self.table_a, "b": self.table_b}[table]
+            if isinstance(src, np.ndarray) or isinstance(self._par, np.ndarray):
+                self._host[key] = P.imp_vs_par(self.cpu(table), par)
+            else:
+                self.cpu(table)   # (refuses a record whose self-check bit is clear)
+                self._host[key] = P.par_imp(src.contiguous(), self._par, 1).cpu().numpy()
+        return self._host[key]
+
+    def boards(self, par=False):
+        """one dict per board: the dataset's fields plus ``table_a`` / ``table_b`` and ``imp``.  ``par=True`` adds
+        ``par`` = {score_ns, contracts, dealer_dependent} to each board and ``imp_vs_par`` to each table."""
+        a = self.cpu("a")
+        dda, ids, imp = self._dda(), self._np("board_id"), self._np("imp")
+        if par:
+            from .par import DEALER_DEPENDENT, par_contracts
+            pr = self.par()
         out = []
         for i in range(len(a)):
             r = a[i]
@@ -336,23 +383,28 @@ class BoardRecords:
                  "deal": {seat: hand_names(r["hands"][s]) for s, seat in enumerate(SEATS)},
                  "vulnerability": VULS[int(r["vul_ns"]) + 2 * int(r["vul_ew"])],
                  "dda": {seat: {st: int(dda[i].reshape(4, 5)[s, d]) for d, st in enumerate(STRAINS)} for s, seat in enumerate(SEATS)},
-                 "table_a": self._table_dict(i, "a")}
+                 "table_a": self._table_dict(i, "a", par)}
             if self.table_b is not None:
-                b["table_b"] = self._table_dict(i, "b")
+                b["table_b"] = self._table_dict(i, "b", par)
             if imp is not None:
                 b["imp"] = int(imp[i])
+            if par:
+                b["par"] = {"score_ns": int(pr[i]["score_ns"]), "contracts": par_contracts(pr[i], dda[i]),
+                            "dealer_dependent": bool(pr[i]["flags"] & DEALER_DEPENDENT)}
             out.append(b)
         return out
 
-    def to_json(self, path):
+    def to_json(self, path, par=False):
         with open(path, "w") as f:
-            json.dump({"logs": self.boards()}, f)
+            json.dump({"logs": self.boards(par)}, f)
 
-    def to_pbn(self, path):
-        """one game per board and table (the second table in the closed room), standard tags"""
+    def to_pbn(self, path, par=False):
+        """one game per board and table (the second table in the closed room), standard tags.  ``par=True`` adds
+        ``OptimumScore`` and ``ParContract`` (side and contract, the lowest one when several score par; ``Pass`` when par is a
+        pass-out)."""
         pbn_call = {"P": "Pass"}
         lines = ["% PBN 2.1", ""]
-        for b in self.boards():
+        for b in self.boards(par):
             dd = "".join(f"{b['dda'][seat][st]:x}" for seat in "NSEW" for st in ("NT", "S", "H", "D", "C"))
             for room, key in (("Open", "table_a"), ("Closed", "table_b")):
                 t = b.get(key)
@@ -364,18 +416,23 @@ class BoardRecords:
                           f'[Deal "{pbn_deal([sum(1 << card_bit(c) for c in b["deal"][s]) for s in SEATS])}"]',
                           f'[Declarer "{t["declarer"] or ""}"]', f'[Contract "{contract}"]',
                           f'[Result "{t["tricks"] if t["tricks"] is not None else ""}"]', f'[Score "NS {t["score_ns"]}"]',
-                          f'[DoubleDummyTricks "{dd}"]', f'[Auction "{b["dealer"]}"]']
+                          f'[DoubleDummyTricks "{dd}"]']
+                if par:
+                    first = b["par"]["contracts"][0].split(" by ") if b["par"]["contracts"] else None
+                    lines += [f'[OptimumScore "NS {b["par"]["score_ns"]}"]',
+                              f'[ParContract "{first[1] + " " + first[0] if first else "Pass"}"]']
+                lines.append(f'[Auction "{b["dealer"]}"]')
                 calls = [pbn_call.get(c, c) for c in t["auction"]]
                 lines += [" ".join(calls[k:k + 4]) for k in range(0, len(calls), 4)]
                 lines.append("")
         with open(path, "w") as f:
             f.write("\n".join(lines))
 
-    def save(self, path):
+    def save(self, path, par=False):
         if str(path).lower().endswith(".pbn"):
-            self.to_pbn(path)
+            self.to_pbn(path, par)
         else:
-            self.to_json(path)
+            self.to_json(path, par)
 
 
 # ---- a match with its boards ------------------------------------------------------------------------------------------------------

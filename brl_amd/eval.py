@@ -2,7 +2,7 @@
 
     python -m brl_amd.eval team1_model_path=a.pt team2_model_path=b.pkl [team2_model_type=FAIR] [num_eval_envs=100] [dds_path=...]
                            [deals_path=deals.json|deals.pbn] [save_boards=out.json|out.pbn]
-                           [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20]
+                           [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20] [par=1]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -10,6 +10,8 @@ The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` 
 dealing from the table; ``save_boards``: write every board's two auctions, contracts, scores and IMP (``boards.BoardRecords``).
 ``save_book``: write the bidding-system book of the match (``book.system_book``: what each call shows, by auction prefix, over
 the first ``book_depth`` calls; entries with fewer than ``book_min_count`` samples are left out) as JSON or, ``.txt``, as a tree.
+``par=1``: the boards are scored against their double-dummy par (``par.par_stats``): one line per team behind the ``IMP:``
+line, and ``save_boards`` writes the par score, the par contracts and each table's IMP against par too.
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     team1_model_path=None, team2_model_path=None, team1_activation="relu", team1_model_type="DeepMind",
     team2_activation="relu", team2_model_type="DeepMind", num_eval_envs=100,
     dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
-    deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20,
+    deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20, par=0,
 )
 
 
@@ -31,7 +33,7 @@ def main(argv, log=print):
     cfg = parse(argv, EVAL_DEFAULTS)
     if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
         raise SystemExit("team1_model_path= and team2_model_path= are required")
-    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None
+    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -49,7 +51,7 @@ def main(argv, log=print):
                                        cfg["team2_model_type"], cfg["num_eval_envs"])
         (imp, se, _), records = board_match(team1, team2, deals if deals is not None else 0)
         if cfg["save_boards"] is not None:
-            records.save(cfg["save_boards"])
+            records.save(cfg["save_boards"], par=bool(cfg["par"]))
             log(f"boards: {cfg['save_boards']}")
         if cfg["save_book"] is not None:
             from .book import system_book
@@ -60,6 +62,10 @@ def main(argv, log=print):
                                                             cfg["team2_model_type"], cfg["num_eval_envs"])
         (imp, se, _), _, _ = duplicate_evaluate(team1, team2, 0)
     log(f"IMP: {float(imp)} ± {float(se)}")
+    if cfg["par"]:
+        from .par import par_stats, stats_lines
+        for line in stats_lines(par_stats(records)):
+            log(line)
     return float(imp), float(se)
 
 
