@@ -257,6 +257,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
+// draw d of a stream is word d & 3 of its Philox block d >> 2
+__device__ __forceinline__ uint32_t philox_word(const uint32_t r[4], uint32_t draw) {
+  const uint32_t sel = draw & 3u, r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // (all four read: selects, no branches)
+  return (sel == 0) ? r0 : ((sel == 1) ? r1 : ((sel == 2) ? r2 : r3));
+}
 
 struct Rng {
   uint32_t k0, k1;  // seed
@@ -327,6 +332,9 @@ __device__ __forceinline__ LaneConst make_lane_const() {
 }
 
 // A3: one table's 480-byte observation row from its LDS image (wb5/utils.py:15-52).
+// 4 bits (nib < 16) -> 4 bytes of 0/1, bit i in byte i
+__device__ __forceinline__ uint32_t nibble_bytes(uint32_t nib) { return __umul24(nib, 0x204081u) & 0x01010101u; }
+
 // Wave-cooperative: lane l produces obs bytes [8l, 8l+8) and the wave issues ONE 8-byte-per-
 // lane store = 480 contiguous bytes.  `seat` (observer seat) and `vulnib` are wave-uniform.
 __device__ __forceinline__ void emit_obs_row(const uint8_t *img, int seat, uint32_t vulnib, uint8_t *dst_row,
@@ -338,8 +346,7 @@ __device__ __forceinline__ void emit_obs_row(const uint8_t *img, int seat, uint3
   uint32_t rot = ((a >> seat) & m1) | ((a << (4 - seat)) & (m1 ^ 0xFFu));
   uint32_t byte = (rot & c.hist_keep) | (h & c.hand_keep);
   byte |= (c.lane == 0) ? vulnib : 0u;
-  uint32_t lo = __umul24(byte & 0xFu, 0x204081u) & 0x01010101u;  // 4 bits -> 4 bytes of 0/1
-  uint32_t hi = __umul24(byte >> 4, 0x204081u) & 0x01010101u;
+  uint32_t lo = nibble_bytes(byte & 0xFu), hi = nibble_bytes(byte >> 4);
   if (c.lane < 60) *reinterpret_cast<uint2 *>(dst_row + c.lane * 8) = make_uint2(lo, hi);
 }
 
@@ -429,7 +436,7 @@ __device__ __forceinline__ uint32_t mask_dword(uint64_t legal_a, uint64_t legal_
   uint32_t sa = (uint32_t)(legal_a >> m.sh);
   uint32_t sb = (uint32_t)legal_b << m.split;
   uint32_t nib = (sa & m.keep_a) | (sb & (0xFu & ~m.keep_a));
-  return __umul24(nib, 0x204081u) & 0x01010101u;
+  return nibble_bytes(nib);
 }
 
 // this lane's 32 observation bytes of its row (seat / vulnib: the row's observer, per lane).
@@ -449,7 +456,7 @@ __device__ __forceinline__ void obs_chunk_store(uint32_t a, uint64_t H, int seat
   uint32_t word = (rot & g.keep_hist) | (hv & g.keep_hand) | (vulnib & g.keep_vul);
   uint32_t d[8];
 #pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = __umul24((word >> (4 * i)) & 0xFu, 0x204081u) & 0x01010101u;
+  for (int i = 0; i < 8; i++) d[i] = nibble_bytes((word >> (4 * i)) & 0xFu);
   uint4 *dst = reinterpret_cast<uint4 *>(dst_group + g.out_off);
   dst[0] = make_uint4(d[0], d[1], d[2], d[3]);
   dst[1] = make_uint4(d[4], d[5], d[6], d[7]);

@@ -35,6 +35,16 @@ struct RolloutArgs {
   float *gae_adv, *gae_tgt;  // [T,n]; gae_adv == NULL: off
 };
 
+// terminated_count += the wave's sum of `v` (G2, src/roll_out.py:85), one atomic per wave; timing builds (dump buffer) add nothing
+__device__ __forceinline__ void add_terminated(unsigned long long *terminated_count, uint32_t v, int lane) {
+  if (terminated_count == nullptr) return;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+#ifndef BRL_TIMING
+  if (lane == 0 && v) atomicAdd(terminated_count, (unsigned long long)v);
+#endif
+}
+
 template <int K>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_rollout_random(RolloutArgs A) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES_PER_BLOCK * K * TABLE_BYTES];
@@ -60,8 +70,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_rollout_random(RolloutArgs A)
         rb_idx = draw >> 2;
         philox4x32_10((uint32_t)env_id, rb_idx, STREAM_ACTION, (uint32_t)(env_id >> 32), A.g.k0, A.g.k1, rb);
       }
-      uint32_t sel = draw & 3u;
-      uint32_t u = (sel == 0) ? rb[0] : ((sel == 1) ? rb[1] : ((sel == 2) ? rb[2] : rb[3]));
+      uint32_t u = philox_word(rb, draw);
       if (k > 0) legal = legal_mask(t);
       int nl;
       int a = random_legal_action(t, legal, u, nl);
@@ -97,17 +106,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_rollout_random(RolloutArgs A)
     int oseat = cur_seat(t);
     wave_emit<K>(w, A.n, oseat, vul_nibble(t, oseat), legal_mask(t), A.last_obs, A.last_mask, w.table0);
   }
-  if (A.terminated_count != nullptr) {  // G2, src/roll_out.py:85
-    uint32_t v = (w.c.lane < K && w.valid) ? tcount : 0u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (w.c.lane == 0 && v) atomicAdd(A.terminated_count, (unsigned long long)v);
-  }
+  add_terminated(A.terminated_count, (w.c.lane < K && w.valid) ? tcount : 0u, w.c.lane);
   wave_end<K>(w, t, A.state, A.n);
 }
 
-// ---- A7 fused random-policy rollout, wave-specialised ("ws"): constants and command format; the kernel and
-// the description of its roles follow below ---------------------------------------------------------------
+// ---- A7 fused random-policy rollout, wave-specialised (k_rollout_ws, k_rollout_fs): constants, the command format and the
+// role bodies both kernels use; k_rollout_ws and the description of the roles follow below -----------------------------
 constexpr int CMD_WORDS = 4;
 constexpr int RING_WORDS = 16;  // hands[8] (the four packed hand words, k_lut_hands) values[4] idx sc_bits pad pad
 constexpr int WS_BATCH = 8;     // sub-steps per workgroup barrier
@@ -118,6 +122,141 @@ constexpr uint32_t NO_SLOT = 0xFFu;  // scorer: the table still plays the board 
 //                about state s: [11:10] observer seat | [15:12] vul nibble
 // word 1: scalar word `sc` right after sub-step s-1 (before any re-deal)
 // word 2: legal mask of state s, low 32 | word 3: [5:0] legal high ; [13:8] action of sub-step s-1
+// Written by k_rollout_ws's logic wave and k_rollout_fs's prep wave, read by every follower role — through these only:
+__device__ __forceinline__ uint32_t cmd_pack_prev(uint32_t hb1, uint32_t deal, uint32_t slot, uint32_t seat, uint32_t n_legal) {
+  return hb1 | (deal << 9) | (slot << 16) | (seat << 21) | (n_legal << 23);  // word 0, the part about sub-step s-1
+}
+__device__ __forceinline__ uint32_t cmd_pack_w0(uint32_t prev, uint32_t observer, uint32_t vulnib) { return prev | (observer << 10) | (vulnib << 12); }
+__device__ __forceinline__ uint32_t cmd_pack_w3(uint64_t legal, uint32_t action) { return ((uint32_t)(legal >> 32) & 63u) | (action << 8); }
+__device__ __forceinline__ uint32_t cmd_hist_bit1(uint32_t w0) { return w0 & 0x1FFu; }  // history bit + 1; 0: none
+__device__ __forceinline__ bool cmd_deal(uint32_t w0) { return (w0 & 0x200u) != 0u; }
+__device__ __forceinline__ uint32_t cmd_ring_slot(uint32_t w0) { return (w0 >> 16) & 15u; }
+__device__ __forceinline__ uint32_t cmd_seat(uint32_t w0) { return (w0 >> 21) & 3u; }  // who acted in sub-step s-1
+__device__ __forceinline__ uint32_t cmd_n_legal(uint32_t w0) { return (w0 >> 23) & 63u; }
+__device__ __forceinline__ uint32_t cmd_observer(uint32_t w0) { return (w0 >> 10) & 3u; }
+__device__ __forceinline__ uint32_t cmd_vul(uint32_t w0) { return (w0 >> 12) & 15u; }
+__device__ __forceinline__ uint32_t cmd_action(uint32_t w3) { return (w3 >> 8) & 63u; }
+// words 2, 3 as one: the legal mask in bits 0..37 (the bits above it are word 3's other fields)
+__device__ __forceinline__ uint64_t cmd_legal(const uint32_t *c) { return *reinterpret_cast<const uint64_t *>(c + 2); }
+
+// ---- role bodies that k_rollout_ws and k_rollout_fs (rollout_fs.hpp) share ----------------------------------------
+// (loader) board `board` of slot env_id: Philox -> LUT row -> its packed hand words + DDS values, 48 B.  The loads are
+// only issued here; board_commit, a batch or a pass later, is the first to wait for them.
+__device__ __forceinline__ void board_fetch(const Rng &g, uint64_t env_id, uint32_t board, const LutRef &lut, brl_u32x4 &ha,
+                                            brl_u32x4 &hb, brl_u32x4 &v, uint32_t &idx, uint32_t &scb) {
+  board_params(g, env_id, board, lut.len, idx, scb);
+  ha = reinterpret_cast<const brl_u32x4 *>(lut.hands)[2 * (size_t)idx];
+  hb = reinterpret_cast<const brl_u32x4 *>(lut.hands)[2 * (size_t)idx + 1];
+  v = reinterpret_cast<const brl_u32x4 *>(lut.values)[idx];
+}
+__device__ __forceinline__ void board_commit(uint32_t *entry, const brl_u32x4 &ha, const brl_u32x4 &hb, const brl_u32x4 &v,
+                                             uint32_t idx, uint32_t scb) {  // entry: RING_WORDS words
+  uint4 *dst = reinterpret_cast<uint4 *>(entry);
+  brl_u32x4 *dv = reinterpret_cast<brl_u32x4 *>(dst);
+  dv[0] = ha;
+  dv[1] = hb;
+  dv[2] = v;
+  dst[3] = make_uint4(idx, scb, 0u, 0u);
+}
+
+// (scorers) info word of a macro-step: [1:0] acting player | [7:2] its action | [13:8] n_legal | [14] done
+constexpr uint32_t INFO_DONE = 1u << 14;
+__device__ __forceinline__ uint32_t info_actor(uint32_t info) { return info & 3u; }
+__device__ __forceinline__ uint32_t info_action(uint32_t info) { return (info >> 2) & 63u; }
+__device__ __forceinline__ uint32_t info_n_legal(uint32_t info) { return (info >> 8) & 63u; }
+__device__ __forceinline__ uint32_t info_done(uint32_t info) { return (info >> 14) & 1u; }
+// queue entry of a finished board: the scalars and first denominations it ended on, step | table << 8, its ring slot
+__device__ __forceinline__ uint32_t ev_step(const uint4 &q) { return q.z & 0xFFu; }
+__device__ __forceinline__ uint32_t ev_table(const uint4 &q) { return (q.z >> 8) & 63u; }
+
+// (scorers, lane = table) One command of the table this lane follows: scalars, first denominations, a finished board into the
+// queue `ev` (compacted over the tables: one lane per board scores them) under `step`, a re-deal.  Returns the info word.
+template <int W>
+__device__ __forceinline__ uint32_t scorer_follow(Tbl &ts, uint32_t &vslot, int &nev, const uint4 &w, bool mine, uint32_t step,
+                                                  uint32_t table, uint32_t (*ev)[W]) {
+  const int a = (int)cmd_action(w.w);
+  const int seat = (int)cmd_seat(w.x);
+  ts.sc = w.y;
+  // the acting player (src/roll_out.py:72), its action, n_legal
+  uint32_t info = (uint32_t)player_at(ts, seat) | ((uint32_t)a << 2) | (cmd_n_legal(w.x) << 8);
+  note_first_denomination(ts.fd, seat, a);
+  const bool fin = mine && bits(ts.sc, SC_TERM, 1);
+  const uint64_t fm = __ballot(fin);
+  if (fm) {
+    if (fin) {
+      const int pos = nev + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+      *reinterpret_cast<uint4 *>(&ev[pos][0]) = make_uint4(ts.sc, ts.fd, step | (table << 8), vslot);
+      info |= INFO_DONE;  // G2
+    }
+    nev += __popcll(fm);
+  }
+  // the slot was re-dealt: no strain named yet; the new board's DDS values stay in its ring entry until the board is
+  // scored (k_rollout_ws's loader frees an entry one board late for that)
+  const bool dealt = cmd_deal(w.x);
+  vslot = dealt ? cmd_ring_slot(w.x) : vslot;
+  ts.fd = dealt ? 0u : ts.fd;
+  return info;
+}
+
+// (scorers) DDS tricks of the board a table plays: entry `slot` of its ring; NO_SLOT (the board it came in with): its packed image
+__device__ __forceinline__ void board_tricks(Tbl &tb, uint32_t slot, const uint32_t (*table_ring)[RING_WORDS], const uint8_t *table_img) {
+  if (slot != NO_SLOT) {
+    const uint4 vv = *reinterpret_cast<const uint4 *>(&table_ring[slot][8]);
+    pack_tricks(tb, vv.x, vv.y, vv.z, vv.w);
+  } else {
+    const uint2 *ip = reinterpret_cast<const uint2 *>(table_img);
+    const uint2 tr = ip[W_TR], fdw = ip[W_FD];
+    tb.t0 = tr.x; tb.t1 = tr.y; tb.t2 = fdw.y;
+  }
+}
+// a queued board -> contract, DDS tricks, score: its reward vector (A4) in the returned table
+__device__ __forceinline__ Tbl score_finished_board(const uint4 &q, const uint32_t (*table_ring)[RING_WORDS], const uint8_t *table_img) {
+  Tbl tb;
+  tb.sc = q.x; tb.fd = q.y;
+  board_tricks(tb, q.w, table_ring, table_img);
+  terminal_reward(tb);  // A4
+  return tb;
+}
+
+// (scorers) four info words — four consecutive tables of one macro-step — as the 16-byte pieces of the action and
+// log_prob columns and the 4 bytes of done (G2); returns how many of the four are done
+__device__ __forceinline__ uint32_t unpack_info4(const uint4 &info4, const float *neglog, brl_u32x4 &act, float4 &lgp, uint32_t &dn) {
+  const uint32_t inf[4] = {info4.x, info4.y, info4.z, info4.w};
+  float lp[4];
+  uint32_t ac[4], count = 0;
+  dn = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    lp[k] = neglog[info_n_legal(inf[k])];
+    ac[k] = info_action(inf[k]);
+    dn |= info_done(inf[k]) << (8 * k);
+    count += info_done(inf[k]);
+  }
+  act = brl_u32x4{ac[0], ac[1], ac[2], ac[3]};
+  lgp = make_float4(lp[0], lp[1], lp[2], lp[3]);
+  return count;
+}
+
+// (mask wave) The 32 legal-mask rows of a sub-step are 1216 contiguous bytes = 76 chunks of 16 B: lane l writes chunk l,
+// lanes < 12 also chunk 64 + l.  A chunk holds the bytes of table ta (from action `off` on) and possibly of ta + 1 (tb).
+struct MaskChunk {
+  uint32_t ta, tb, off;
+};
+__device__ __forceinline__ MaskChunk make_mask_chunk(uint32_t cidx, uint32_t tables) {
+  MaskChunk m;
+  const uint32_t byte0 = 16u * ((cidx < 76u) ? cidx : 75u);
+  m.ta = byte0 / BRL_NUM_ACTIONS;
+  m.off = byte0 - m.ta * BRL_NUM_ACTIONS;
+  m.tb = (m.ta + 1u < tables) ? m.ta + 1u : m.ta;
+  return m;
+}
+__device__ __forceinline__ brl_u32x4 mask_chunk_bytes(const uint32_t (*cs)[CMD_WORDS], const MaskChunk &m) {  // cs: a sub-step's commands
+  const uint64_t la = cmd_legal(cs[m.ta]) & ALL_ACTIONS;
+  const uint64_t lb = cmd_legal(cs[m.tb]) & ALL_ACTIONS;
+  const uint32_t bits16 = (uint32_t)((la >> m.off) | (lb << (BRL_NUM_ACTIONS - m.off)));
+  return brl_u32x4{nibble_bytes(bits16 & 0xFu), nibble_bytes((bits16 >> 4) & 0xFu), nibble_bytes((bits16 >> 8) & 0xFu),
+                   nibble_bytes((bits16 >> 12) & 0xFu)};
+}
 
 // Command batches: ONE slot first, so that the follower waves — and with them the HBM stores, which the launch is
 // bound by once its output is larger than the Infinity Cache — start after one sub-step instead of eight; then 3, 4 and
@@ -240,8 +379,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         rbk_idx = draw >> 2;
         philox4x32_10((uint32_t)env_id, rbk_idx, STREAM_ACTION, (uint32_t)(env_id >> 32), A.g.k0, A.g.k1, rbk);
       }
-      const uint32_t sel = draw & 3u;
-      if (tl < TPB) udraw[b & 1][j][tl] = (sel == 0) ? rbk[0] : ((sel == 1) ? rbk[1] : ((sel == 2) ? rbk[2] : rbk[3]));
+      if (tl < TPB) udraw[b & 1][j][tl] = philox_word(rbk, draw);
     }
   };
   if (wave == 1) draws(0);
@@ -260,12 +398,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
     pcount = lup ? 1u : 2u;
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      if ((uint32_t)k < pcount) {
-        board_params(A.g, eid, pbase + (uint32_t)k, A.lut.len, pidx[k], pscb[k]);
-        pha[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)pidx[k]];
-        phb[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)pidx[k] + 1];
-        pv[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.values)[pidx[k]];
-      }
+      if ((uint32_t)k < pcount) board_fetch(A.g, eid, pbase + (uint32_t)k, A.lut, pha[k], phb[k], pv[k], pidx[k], pscb[k]);
     }
     nb = nb0 + ((TPB == 32) ? 3u : 2u);
   }
@@ -280,14 +413,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
       // commit what was issued one batch ago (its loads landed long before)
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        if ((uint32_t)k < pcount) {
-          uint4 *dst = reinterpret_cast<uint4 *>(&ring[lt][(pbase + (uint32_t)k) % WS_RING][0]);
-          brl_u32x4 *dv = reinterpret_cast<brl_u32x4 *>(dst);
-          dv[0] = pha[k];
-          dv[1] = phb[k];
-          dv[2] = pv[k];
-          dst[3] = make_uint4(pidx[k], pscb[k], 0u, 0u);
-        }
+        if ((uint32_t)k < pcount) board_commit(&ring[lt][(pbase + (uint32_t)k) % WS_RING][0], pha[k], phb[k], pv[k], pidx[k], pscb[k]);
       }
       pcount = 0;
       if (bi == 0) {  // the first three boards are in the ring now
@@ -297,7 +423,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
       uint32_t dealt = 0;  // boards this table consumed in batch bi
       for (int j = 0; j < ws_blen(bi); j++) {
         const int s = ws_bstart(bi) + j;
-        if (s <= total) dealt += (cmd[bi & 1][j][tls][0] >> 9) & 1u;
+        if (s <= total) dealt += cmd_deal(cmd[bi & 1][j][tls][0]) ? 1u : 0u;
       }
       // keep WS_RING boards ahead of what had been consumed by the end of batch bi-1 (slots of boards
       // dealt in batch bi are still being read by the scorer / emit waves): at most 3 fetches per batch,
@@ -308,12 +434,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         pcount = min(3u, want - nb);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-          if ((uint32_t)k < pcount) {
-            board_params(A.g, env_id, nb + (uint32_t)k, A.lut.len, pidx[k], pscb[k]);
-            pha[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)pidx[k]];
-            phb[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)pidx[k] + 1];
-            pv[k] = reinterpret_cast<const brl_u32x4 *>(A.lut.values)[pidx[k]];
-          }
+          if ((uint32_t)k < pcount) board_fetch(A.g, env_id, nb + (uint32_t)k, A.lut, pha[k], phb[k], pv[k], pidx[k], pscb[k]);
         }
         nb += pcount;
       }
@@ -346,9 +467,8 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         uint32_t nsc = sc, nsch = sch;
         const LeanStep st = lean_random_step(nsc, nsch, u);
         if (tl < TPB) {  // command slot s: what sub-step s-1 did + how state s looks
-          uint32_t w0 = pend | ((uint32_t)st.seat << 10) | (vul_nibble_sc(sc, st.seat) << 12);
-          uint32_t w3 = ((uint32_t)(st.legal >> 32) & 63u) | (pend_act << 8);
-          *reinterpret_cast<uint4 *>(&cmd[bi & 1][j][tl][0]) = make_uint4(w0, pend_sc, (uint32_t)st.legal, w3);
+          const uint32_t w0 = cmd_pack_w0(pend, (uint32_t)st.seat, vul_nibble_sc(sc, st.seat));
+          *reinterpret_cast<uint4 *>(&cmd[bi & 1][j][tl][0]) = make_uint4(w0, pend_sc, (uint32_t)st.legal, cmd_pack_w3(st.legal, pend_act));
         }
         // the barrier that publishes a batch sits right after its LAST post — before that sub-step is
         // committed — so followers start one sub-step earlier and a deal at sub-step 0 can wait for ring_ready
@@ -365,7 +485,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         pend_act = (uint32_t)st.action;
         const bool deal = valid && st.term;
         const uint32_t slot = (bctr + 1u) % WS_RING;
-        pend = st.hb1 | ((uint32_t)deal << 9) | (slot << 16) | ((uint32_t)st.seat << 21) | ((uint32_t)st.n_legal << 23);
+        pend = cmd_pack_prev(st.hb1, (uint32_t)deal, slot, (uint32_t)st.seat, (uint32_t)st.n_legal);
         if (!have_nxt && __any(deal)) {  // uniform: first deal of the wave
           while (__hip_atomic_load(&ring_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
           nxt = *reinterpret_cast<const uint2 *>(&ring[tls][(bctr + 1u) % WS_RING][12]);
@@ -422,28 +542,9 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         const uint4 w = wn;  // the next command is fetched while this one is processed
         wn = *reinterpret_cast<const uint4 *>(&cmd[bi & 1][(j + 1 < blen) ? j + 1 : j][tls][0]);
         if (s == 0) continue;  // cmd slot 0 describes no sub-step
-        const int a = (int)((w.w >> 8) & 63u);
-        const int seat = (int)((w.x >> 21) & 3u);
-        ts.sc = w.y;
-        if (sub == 0)  // first sub-step of a macro-step: the acting player (src/roll_out.py:72), its action
-          cur_info = (uint32_t)player_at(ts, seat) | ((uint32_t)a << 2) | (((w.x >> 23) & 63u) << 8);
-        note_first_denomination(ts.fd, seat, a);
-        const bool fin = (tl < TPB) && bits(ts.sc, SC_TERM, 1);
-        const uint64_t fm = __ballot(fin);
-        if (fm) {  // queue the finished boards for pass 2, compacted over the tables: one lane per board there
-          if (fin) {
-            const int pos = nev + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-            *reinterpret_cast<uint4 *>(&ev[pos][0]) = make_uint4(ts.sc, ts.fd, (uint32_t)m | ((uint32_t)tl << 8), vslot);
-            cur_info |= 1u << 14;  // done (G2)
-          }
-          nev += __popcll(fm);
-        }
-        {  // the slot was re-dealt: no strain named yet; the new board's DDS values stay in its ring entry until
-           // the board is scored (the loader frees an entry one board late for that)
-          const bool dealt = (w.x & 0x200u) != 0u;
-          vslot = dealt ? ((w.x >> 16) & 15u) : vslot;
-          ts.fd = dealt ? 0u : ts.fd;
-        }
+        const uint32_t info = scorer_follow(ts, vslot, nev, w, tl < TPB, (uint32_t)m, (uint32_t)tl, ev);
+        // actor, action and n_legal are those of the macro-step's first sub-step; done: a board ended in any of them
+        cur_info = (sub == 0) ? info : (cur_info | (info & INFO_DONE));
         if (++sub == A.substeps) {
           sub = 0;
           minfo[m][tl] = cur_info;
@@ -459,19 +560,9 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         const int e = e0 + c.lane;
         if (e < nev) {
           const uint4 q = *reinterpret_cast<const uint4 *>(&ev[e][0]);
-          const uint32_t tt = (q.z >> 8) & 63u;
-          Tbl tb;
-          tb.sc = q.x; tb.fd = q.y;
-          if (q.w != NO_SLOT) {  // a board dealt in this launch: DDS values from its ring entry
-            const uint4 vv = *reinterpret_cast<const uint4 *>(&ring[tt][q.w][8]);
-            pack_tricks(tb, vv.x, vv.y, vv.z, vv.w);
-          } else {          // the board the table came in with: its tricks are in the packed image
-            const uint2 *ip = reinterpret_cast<const uint2 *>(img + tt * TABLE_BYTES);
-            const uint2 tr = ip[W_TR], fdw = ip[W_FD];
-            tb.t0 = tr.x; tb.t1 = tr.y; tb.t2 = fdw.y;
-          }
-          terminal_reward(tb);  // A4
-          int *ac = &acc[q.z & (WS_BATCH - 1)][tt][0];
+          const uint32_t tt = ev_table(q);
+          const Tbl tb = score_finished_board(q, ring[tt], img + tt * TABLE_BYTES);
+          int *ac = &acc[ev_step(q) & (WS_BATCH - 1)][tt][0];
           atomicAdd(&ac[0], reward_of(tb, 0)); atomicAdd(&ac[1], reward_of(tb, 1));  // (substeps >= 8: two boards of a
           atomicAdd(&ac[2], reward_of(tb, 2)); atomicAdd(&ac[3], reward_of(tb, 3));  //  table can end in one macro-step)
         }
@@ -495,25 +586,23 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
         if (q < m) {
           const uint4 info4 = *reinterpret_cast<const uint4 *>(&minfo[q][t4]);
           const uint32_t inf[4] = {info4.x, info4.y, info4.z, info4.w};
-          float rew[4], lgp[4];
-          uint32_t act[4], dn = 0;
+          float rew[4];
 #pragma unroll
           for (int k = 0; k < 4; k++) {
             const int4 r = *reinterpret_cast<const int4 *>(&acc[q][t4 + k][0]);
-            const int actor = (int)(inf[k] & 3u);
+            const int actor = (int)info_actor(inf[k]);
             const int ra = (actor == 0) ? r.x : ((actor == 1) ? r.y : ((actor == 2) ? r.z : r.w));
             rew[k] = (float)ra / A.reward_scale;  // G1, src/roll_out.py:90
-            lgp[k] = s_neglog[(inf[k] >> 8) & 63u];
-            act[k] = (inf[k] >> 2) & 63u;
-            const uint32_t done = (inf[k] >> 14) & 1u;
-            dn |= done << (8 * k);
-            tcount += done;
           }
+          brl_u32x4 act;
+          float4 lgp;
+          uint32_t dn;
+          tcount += unpack_info4(info4, s_neglog, act, lgp, dn);
           const int64_t rw = (row - tl) + (int64_t)q * A.n + t4;  // row - tl: the workgroup's first table at this macro-step
-          *reinterpret_cast<brl_u32x4 *>(A.out.action + rw) = brl_u32x4{act[0], act[1], act[2], act[3]};
+          *reinterpret_cast<brl_u32x4 *>(A.out.action + rw) = act;
           *reinterpret_cast<float4 *>(A.out.value + rw) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           *reinterpret_cast<float4 *>(A.out.reward + rw) = make_float4(rew[0], rew[1], rew[2], rew[3]);
-          *reinterpret_cast<float4 *>(A.out.log_prob + rw) = make_float4(lgp[0], lgp[1], lgp[2], lgp[3]);
+          *reinterpret_cast<float4 *>(A.out.log_prob + rw) = lgp;
           *reinterpret_cast<uint32_t *>(A.out.done + rw) = dn;  // G2
         }
         row += (int64_t)m * A.n;
@@ -528,15 +617,15 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
           if (q < m && vq) {
             const uint32_t info = minfo[q][tq];
             const int4 r = *reinterpret_cast<const int4 *>(&acc[q][tq][0]);
-            const int actor = (int)(info & 3u);
+            const int actor = (int)info_actor(info);
             const int ra = (actor == 0) ? r.x : ((actor == 1) ? r.y : ((actor == 2) ? r.z : r.w));
-            const uint32_t done = (info >> 14) & 1u;
+            const uint32_t done = info_done(info);
             const int64_t rw = row + (int64_t)q * A.n + (tq - tl);
             if (A.out.done) A.out.done[rw] = (uint8_t)done;  // G2
-            if (A.out.action) A.out.action[rw] = (int32_t)((info >> 2) & 63u);
+            if (A.out.action) A.out.action[rw] = (int32_t)info_action(info);
             if (A.out.value) A.out.value[rw] = 0.0f;
             if (A.out.reward) A.out.reward[rw] = (float)ra / A.reward_scale;  // G1, src/roll_out.py:90
-            if (A.out.log_prob) A.out.log_prob[rw] = s_neglog[(info >> 8) & 63u];
+            if (A.out.log_prob) A.out.log_prob[rw] = s_neglog[info_n_legal(info)];
             tcount += done;
           }
         }
@@ -549,19 +638,9 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
       }
     }
     set_rewards(ts, last_acc.x, last_acc.y, last_acc.z, last_acc.w);  // rewards of the last macro-step (src/utils.py:126)
-    if (A.terminated_count != nullptr) {  // src/roll_out.py:85
-      uint32_t v = tcount;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-#ifndef BRL_TIMING
-      if (c.lane == 0 && v) atomicAdd(A.terminated_count, (unsigned long long)v);
-#endif
-    }
+    add_terminated(A.terminated_count, tcount, c.lane);
     if (tl < TPB) {
-      if (vslot != NO_SLOT) {
-        const uint4 vv = *reinterpret_cast<const uint4 *>(&ring[tl][vslot][8]);
-        pack_tricks(ts, vv.x, vv.y, vv.z, vv.w);
-      }
+      board_tricks(ts, vslot, ring[tl], img + tl * TABLE_BYTES);  // of the board the table now plays
       uint2 *p = reinterpret_cast<uint2 *>(img + tl * TABLE_BYTES);
       p[W_FD] = make_uint2(ts.fd, ts.t2);
       p[W_TR] = make_uint2(ts.t0, ts.t1);
@@ -569,17 +648,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
     }
   } else if (MW != 0 && wave == NW - 1) {
     // ------------------------------------------------------------------ mask wave
-    // The 32 legal-mask rows of a sub-step are 1216 contiguous bytes = 76 chunks of 16 B: lane l writes chunk l, lanes
-    // < 12 also chunk 64 + l.  A chunk holds the bytes of table ta (from action `off` on) and possibly of ta + 1.
-    uint32_t ta[2], tb[2], off[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const uint32_t cidx = (uint32_t)c.lane + 64u * (uint32_t)q;
-      const uint32_t byte0 = 16u * ((cidx < 76u) ? cidx : 75u);
-      ta[q] = byte0 / BRL_NUM_ACTIONS;
-      off[q] = byte0 - ta[q] * BRL_NUM_ACTIONS;
-      tb[q] = (ta[q] + 1u < (uint32_t)TPB) ? ta[q] + 1u : ta[q];
-    }
+    const MaskChunk mc[2] = {make_mask_chunk((uint32_t)c.lane, TPB), make_mask_chunk((uint32_t)c.lane + 64u, TPB)};
     uint8_t *mrow = A.out.legal_action_mask + table0 * BRL_NUM_ACTIONS;
     const int64_t mstep = A.n * BRL_NUM_ACTIONS;
     for (int bi = 0; bi < nbatch; bi++) {
@@ -591,13 +660,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
           if (q == 1 && c.lane >= 12) break;
-          const uint64_t la = *reinterpret_cast<const uint64_t *>(&cs[ta[q]][2]) & ALL_ACTIONS;
-          const uint64_t lb = *reinterpret_cast<const uint64_t *>(&cs[tb[q]][2]) & ALL_ACTIONS;
-          const uint32_t bits16 = (uint32_t)((la >> off[q]) | (lb << (BRL_NUM_ACTIONS - off[q])));
-          uint32_t d[4];
-#pragma unroll
-          for (int i = 0; i < 4; i++) d[i] = __umul24((bits16 >> (4 * i)) & 0xFu, 0x204081u) & 0x01010101u;
-          *reinterpret_cast<uint4 *>(mrow + 16 * (c.lane + 64 * q)) = make_uint4(d[0], d[1], d[2], d[3]);
+          *reinterpret_cast<brl_u32x4 *>(mrow + 16 * (c.lane + 64 * q)) = mask_chunk_bytes(cs, mc[q]);
         }
         mrow += mstep;
       }
@@ -650,31 +713,30 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
             const int g = (wave - 3) + k * NE;
             uint8_t *img_g = img + 4 * g * TABLE_BYTES;
             const uint32_t w0 = cs[4 * g + rr][0];
-            if (head && !(w0 & 0x200u) && (w0 & 0x1FFu)) {
-              int hb = (int)(w0 & 0x1FFu) - 1;
+            if (head && !cmd_deal(w0) && cmd_hist_bit1(w0)) {
+              int hb = (int)cmd_hist_bit1(w0) - 1;
               atomicOr(reinterpret_cast<uint32_t *>(img_g + gl.r * TABLE_BYTES) + (hb >> 5), 1u << (hb & 31));
             }
-            uint64_t dealm = __ballot(head && (w0 & 0x200u));
+            uint64_t dealm = __ballot(head && cmd_deal(w0));
             while (dealm) {  // rare: ~1 table in 25 per sub-step
               const int l = __ffsll((unsigned long long)dealm) - 1;  // lane 15*q holds row q's command
               dealm &= dealm - 1ull;
               const int q = l / 15;
               const uint32_t wq = __builtin_amdgcn_readlane(w0, l);
-              deal_hands(img_g + q * TABLE_BYTES, &ring[4 * g + q][(wq >> 16) & 15u][0], c);
+              deal_hands(img_g + q * TABLE_BYTES, &ring[4 * g + q][cmd_ring_slot(wq)][0], c);
             }
             wave_lds_order();
             uint32_t a;
             uint64_t H;
-            obs_chunk_load(img_g, (int)((w0 >> 10) & 3u), gl, a, H);
+            obs_chunk_load(img_g, (int)cmd_observer(w0), gl, a, H);
             {
               GroupLane gz = gl;
               gz.out_off = 0;
-              if (olane) obs_chunk_store(a, H, (int)((w0 >> 10) & 3u), (w0 >> 12) & 15u, optr[k], gz);
+              if (olane) obs_chunk_store(a, H, (int)cmd_observer(w0), cmd_vul(w0), optr[k], gz);
             }
             optr[k] += ostep;
             if (!mask_by_wave) {  // (uniform)
-              const uint64_t la = *reinterpret_cast<const uint64_t *>(&cs[4 * g + ml.qa][2]);
-              const uint64_t lb = *reinterpret_cast<const uint64_t *>(&cs[4 * g + ml.qb][2]);
+              const uint64_t la = cmd_legal(cs[4 * g + ml.qa]), lb = cmd_legal(cs[4 * g + ml.qb]);
               if (ml.active) *mptr[k] = mask_dword(la, lb, ml);
               mptr[k] = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(mptr[k]) + mstep);
             }
@@ -711,25 +773,25 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
           if (left[k] <= 0) continue;
           uint8_t *img_g = img + 4 * g * TABLE_BYTES;
           const bool is_head = head && (gl.r < left[k]);
-          if (is_head && !(w0[k] & 0x200u) && (w0[k] & 0x1FFu)) {
-            int hb = (int)(w0[k] & 0x1FFu) - 1;
+          if (is_head && !cmd_deal(w0[k]) && cmd_hist_bit1(w0[k])) {
+            int hb = (int)cmd_hist_bit1(w0[k]) - 1;
             atomicOr(reinterpret_cast<uint32_t *>(img_g + gl.r * TABLE_BYTES) + (hb >> 5), 1u << (hb & 31));
           }
-          uint64_t dealm = __ballot(is_head && (w0[k] & 0x200u));
+          uint64_t dealm = __ballot(is_head && cmd_deal(w0[k]));
           if (dealm) {  // rare: ~1 table in 25 per sub-step
             do {
               const int l = __ffsll((unsigned long long)dealm) - 1;  // lane 15*q holds row q's command
               dealm &= dealm - 1ull;
               const int q = l / 15;
               const uint32_t wq = __builtin_amdgcn_readlane(w0[k], l);
-              deal_hands(img_g + q * TABLE_BYTES, &ring[4 * g + q][(wq >> 16) & 15u][0], c);
+              deal_hands(img_g + q * TABLE_BYTES, &ring[4 * g + q][cmd_ring_slot(wq)][0], c);
             } while (dealm);
           }
           wave_lds_order();
           if (emit) {
-            obs_chunk_load(img_g, (int)((w0[k] >> 10) & 3u), gl, a[k], H[k]);
-            la[k] = *reinterpret_cast<const uint64_t *>(&cs[4 * g + ml.qa][2]);
-            lb[k] = *reinterpret_cast<const uint64_t *>(&cs[4 * g + ml.qb][2]);
+            obs_chunk_load(img_g, (int)cmd_observer(w0[k]), gl, a[k], H[k]);
+            la[k] = cmd_legal(cs[4 * g + ml.qa]);
+            lb[k] = cmd_legal(cs[4 * g + ml.qb]);
           }
         }
         if (emit) {
@@ -739,8 +801,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
             if (left[k] <= 0) continue;
             // ---- the 4 observation rows: two 16-B stores per lane
             if (gl.r < left[k] && obs_base)
-              obs_chunk_store(a[k], H[k], (int)((w0[k] >> 10) & 3u), (w0[k] >> 12) & 15u,
-                              obs_base + (rowb + 4 * g) * BRL_OBS_SIZE, gl);
+              obs_chunk_store(a[k], H[k], (int)cmd_observer(w0[k]), cmd_vul(w0[k]), obs_base + (rowb + 4 * g) * BRL_OBS_SIZE, gl);
             // ---- the 4 mask rows
             if (mask_base) {
               uint8_t *mdst = mask_base + (rowb + 4 * g) * BRL_NUM_ACTIONS;
@@ -748,8 +809,7 @@ __global__ __launch_bounds__(NW * 64) void k_rollout_ws(RolloutArgs A) {
                 if (ml.active) reinterpret_cast<uint32_t *>(mdst)[c.lane] = mask_dword(la[k], lb[k], ml);
               } else {  // ragged tail of the batch: row by row
                 for (int q = 0; q < left[k]; q++) {
-                  uint64_t lq = *reinterpret_cast<const uint64_t *>(&cs[4 * g + q][2]);
-                  emit_mask_row(lq, mdst + q * BRL_NUM_ACTIONS, c);
+                  emit_mask_row(cmd_legal(cs[4 * g + q]), mdst + q * BRL_NUM_ACTIONS, c);
                 }
               }
             }
@@ -949,8 +1009,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_policy_step(PolicyArgs A) {
     const uint64_t env_id = cx.env_offset + (uint64_t)w.table;
     const uint32_t draw = A.draw + (A.draw_dev ? *A.draw_dev : 0u);
     philox4x32_10((uint32_t)env_id, draw >> 2, STREAM_ACTION, (uint32_t)(env_id >> 32), cx.g.k0, cx.g.k1, r);
-    const uint32_t sel = draw & 3u;
-    u32 = (sel == 0) ? r[0] : ((sel == 1) ? r[1] : ((sel == 2) ? r[2] : r[3]));
+    u32 = philox_word(r, draw);
   }
   float lp;
   const int act = HEADS ? categorical<K>(&hd_logits[0][0], (int64_t)((int)(threadIdx.x >> 6) * K + w.tl) * (POL_HD + 1), 0, w.valid, cand,
@@ -1033,16 +1092,14 @@ static bool transition_aligned(const brl_transition *o, const void *last_obs, co
          aligned_to(last_mask, 16) && aligned_to(adv, 16) && aligned_to(tgt, 16);
 }
 
-extern "C" int brl_rollout_random(brl_handle *h, uint64_t *state, int64_t n, int num_steps, int substeps,
-                                  uint32_t draw_base, float reward_scale, const brl_transition *out,
-                                  uint8_t *last_obs, uint8_t *last_mask, int64_t *terminated_count, void *stream) {
-  COMMON(h, n);
-  NEED(state && out, "state / out");
-  NEED(aligned_to(state, 16) && transition_aligned(out, last_obs, last_mask, nullptr, nullptr),
-       "output arrays must be 16-byte aligned (done: 4-byte)");
-  NEED(num_steps >= 0, "num_steps");
-  NEED(substeps >= 1 && substeps <= 16, "substeps");
-  if (h->lut_len == 0) return fail(BRL_E_NOLUT, "brl_rollout_random auto-resets and needs a LUT%s", "");
+// k_rollout_fs and the one-launch GAE serve a Transition of which no column is left out
+static bool every_column(const brl_transition *o) {
+  return o->obs && o->legal_action_mask && o->done && o->action && o->value && o->reward && o->log_prob;
+}
+// what every fused rollout launch is given (no GAE in the launch: brl_rollout_random_gae adds it)
+static RolloutArgs rollout_args(brl_handle *h, uint64_t *state, int64_t n, int num_steps, int substeps, uint32_t draw_base,
+                                float reward_scale, const brl_transition *out, uint8_t *last_obs, uint8_t *last_mask,
+                                int64_t *terminated_count) {
   RolloutArgs A;
   A.state = state; A.n = n; A.T = num_steps; A.substeps = substeps; A.draw_base = draw_base;
   A.reward_scale = reward_scale; A.g = rng_of(h); A.env_offset = h->env_offset; A.lut = lut_of(h);
@@ -1054,10 +1111,23 @@ extern "C" int brl_rollout_random(brl_handle *h, uint64_t *state, int64_t n, int
 #else
   A.debug = 0;
 #endif
+  return A;
+}
+
+extern "C" int brl_rollout_random(brl_handle *h, uint64_t *state, int64_t n, int num_steps, int substeps,
+                                  uint32_t draw_base, float reward_scale, const brl_transition *out,
+                                  uint8_t *last_obs, uint8_t *last_mask, int64_t *terminated_count, void *stream) {
+  COMMON(h, n);
+  NEED(state && out, "state / out");
+  NEED(aligned_to(state, 16) && transition_aligned(out, last_obs, last_mask, nullptr, nullptr),
+       "output arrays must be 16-byte aligned (done: 4-byte)");
+  NEED(num_steps >= 0, "num_steps");
+  NEED(substeps >= 1 && substeps <= 16, "substeps");
+  if (h->lut_len == 0) return fail(BRL_E_NOLUT, "brl_rollout_random auto-resets and needs a LUT%s", "");
+  const RolloutArgs A = rollout_args(h, state, n, num_steps, substeps, draw_base, reward_scale, out, last_obs, last_mask, terminated_count);
   // the wave-specialised kernel serves a macro-step that spans <= 2 command batches; longer ones (and BRL_ROLLOUT_WS=0)
   // take the K-tables-per-wave kernel
-  const bool all_cols = out->obs && out->legal_action_mask && out->done && out->action && out->value && out->reward && out->log_prob;
-  if (h->ws && h->fs && substeps == 1 && n % FS_TPB == 0 && all_cols) {
+  if (h->ws && h->fs && substeps == 1 && n % FS_TPB == 0 && every_column(out)) {
     // the BASELINE shape: flag-synchronised kernel (rollout_fs.hpp).  It holds a whole launch's commands in LDS (<= 40 steps):
     // a longer rollout is the same thing in pieces — every piece continues from the state, the draw counter and the
     // terminated count the one before left (the pieces are of near-equal length: 64 -> 32 + 32, 100 -> 34 + 33 + 33)
@@ -1103,8 +1173,7 @@ extern "C" int brl_rollout_random_gae(brl_handle *h, uint64_t *state, int64_t n,
   NEED(aligned_to(state, 16) && transition_aligned(out, last_obs, last_mask, advantages, targets),
        "output arrays must be 16-byte aligned (done: 4-byte)");
   if (h->lut_len == 0) return fail(BRL_E_NOLUT, "brl_rollout_random_gae auto-resets and needs a LUT%s", "");
-  const bool all_cols = out->obs && out->legal_action_mask && out->action && out->log_prob;
-  if (!(h->ws && h->fs && num_steps <= FS_MAX_TOTAL && n % FS_TPB == 0 && all_cols)) {
+  if (!(h->ws && h->fs && num_steps <= FS_MAX_TOTAL && n % FS_TPB == 0 && every_column(out))) {
     // shapes the one-launch kernel does not serve (more than 40 steps, n not a multiple of 32, a column left out): the same
     // results from the rollout launch(es) followed by the scan of their columns
     const int rc = brl_rollout_random(h, state, n, num_steps, 1, draw_base, reward_scale, out, last_obs, last_mask,
@@ -1112,11 +1181,7 @@ extern "C" int brl_rollout_random_gae(brl_handle *h, uint64_t *state, int64_t n,
     if (rc != BRL_OK) return rc;
     return brl_gae(h, out->done, out->value, out->reward, last_val, gamma, gamma_lambda, num_steps, n, advantages, targets, stream);
   }
-  RolloutArgs A;
-  A.state = state; A.n = n; A.T = num_steps; A.substeps = 1; A.draw_base = draw_base;
-  A.reward_scale = reward_scale; A.g = rng_of(h); A.env_offset = h->env_offset; A.lut = lut_of(h);
-  A.neg_log_n = h->neg_log_n; A.out = *out; A.terminated_count = (unsigned long long *)terminated_count;
-  A.last_obs = last_obs; A.last_mask = last_mask; A.debug = 0;
+  RolloutArgs A = rollout_args(h, state, n, num_steps, 1, draw_base, reward_scale, out, last_obs, last_mask, terminated_count);
   A.gae_last_val = last_val; A.gae_gamma = gamma; A.gae_gamma_lambda = gamma_lambda; A.gae_adv = advantages; A.gae_tgt = targets;
   hipLaunchKernelGGL(k_rollout_fs, dim3((unsigned)(n / FS_TPB)), dim3(FS_NW * 64), 0, (hipStream_t)stream, A);
   HIP_TRY(hipGetLastError());

@@ -1,5 +1,7 @@
 // rollout_fs.hpp — k_rollout_fs: the fused random-policy rollout (A7, src/roll_out.py:63-107 with a uniform random legal policy),
-// flag-synchronised.  Included by brl_rollout.hip after k_rollout_ws (shares RolloutArgs, the command format and LutRef).
+// flag-synchronised.  Included by brl_rollout.hip after k_rollout_ws: RolloutArgs, the command format (cmd_*) and the role bodies
+// both kernels use (board_fetch / board_commit, scorer_follow, score_finished_board, unpack_info4, mask_chunk_bytes,
+// add_terminated) stand there, ahead of k_rollout_ws; here is what differs: synchronisation, observer images, stores.
 //
 // Same roles as k_rollout_ws — one workgroup owns 32 consecutive tables; a LOGIC wave runs the per-table dependency chain,
 // a LOADER fetches boards, a SCORER writes the scalar Transition columns, EMIT waves write observations — but NO workgroup
@@ -153,18 +155,11 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
   auto ld_issue = [&](int i) {
     const uint64_t eid = A.env_offset + (uint64_t)(table0 + lt);
     const uint32_t nb0 = (uint32_t)(ctr_word >> 32) + 1u;
-    board_params(A.g, eid, nb0 + (uint32_t)(2 * i + ld_half), A.lut.len, ld_idx[i], ld_scb[i]);
-    ld_ha[i] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)ld_idx[i]];
-    ld_hb[i] = reinterpret_cast<const brl_u32x4 *>(A.lut.hands)[2 * (size_t)ld_idx[i] + 1];
-    ld_v[i] = reinterpret_cast<const brl_u32x4 *>(A.lut.values)[ld_idx[i]];
+    board_fetch(A.g, eid, nb0 + (uint32_t)(2 * i + ld_half), A.lut, ld_ha[i], ld_hb[i], ld_v[i], ld_idx[i], ld_scb[i]);
   };
   auto ld_commit = [&](int i) {
-    uint4 *dst = reinterpret_cast<uint4 *>(&ring[lt][2 * i + ld_half][0]);  // entry j = the j-th board dealt in this launch
-    brl_u32x4 *dv = reinterpret_cast<brl_u32x4 *>(dst);
-    dv[0] = ld_ha[i];
-    dv[1] = ld_hb[i];
-    dv[2] = ld_v[i];
-    dst[3] = make_uint4(ld_idx[i], ld_scb[i], 0u, 0u);
+    // entry j = the j-th board dealt in this launch
+    board_commit(&ring[lt][2 * i + ld_half][0], ld_ha[i], ld_hb[i], ld_v[i], ld_idx[i], ld_scb[i]);
     if (c.lane == 0) fs_flag_write(&ring_count, 2 * i + 2);
   };
   if (wave == 1) {
@@ -303,7 +298,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
           }
 #pragma unroll
           for (int k = 0; k < 8; k++) {
-            const float nd = ((mi[k] >> 14) & 1u) ? 0.0f : 1.0f;                                   // 1 - done, src/gae.py:27
+            const float nd = info_done(mi[k]) ? 0.0f : 1.0f;                                       // 1 - done, src/gae.py:27
             const float gnv = (k == 0 && t1 == total) ? A.gae_gamma * next_value : g0;
             const float delta = rr[k] + gnv * nd - 0.0f;                                           // src/gae.py:28 (value == 0)
             gae = delta + A.gae_gamma_lambda * nd * gae;                                           // src/gae.py:29
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
     }
   } else if (wave == 12) {
     // ------------------------------------------------------------------ prep wave: raw -> command, two slots per pass
-    // (lanes 0..31: slot s, lanes 32..63: slot s + 1 when it is already there).  Command format: brl_rollout.hip (k_rollout_ws).
+    // (lanes 0..31: slot s, lanes 32..63: slot s + 1 when it is already there).  Command format: cmd_* in brl_rollout.hip.
     int avail = 0;
     int s = 0;
     while (s <= total) {
@@ -342,11 +337,10 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
         (void)lean_legal(prv.x, seatp, nl_prv);
         const uint32_t a = cur.z & 63u;
         const uint32_t hb1 = lean_hb1(bits(prv.x, SC_LB1, 6), seatp, a);
-        uint32_t pend = hb1 | (((cur.z >> 8) & 1u) << 9) | (((cur.z >> 16) & 15u) << 16) | (seatp << 21) | (nl_prv << 23);
+        uint32_t pend = cmd_pack_prev(hb1, (cur.z >> 8) & 1u, (cur.z >> 16) & 15u, seatp, nl_prv);
         pend = (ms > 0) ? pend : 0u;
-        const uint32_t w0 = pend | (seat << 10);
-        const uint32_t w3 = ((uint32_t)(legal >> 32) & 63u) | (a << 8);
-        *reinterpret_cast<uint4 *>(&cmd[ms][lt][0]) = make_uint4(w0, cur.w, (uint32_t)legal, w3);
+        const uint32_t w0 = cmd_pack_w0(pend, seat, 0u);  // (no vulnerability nibble: the emit waves' observer images hold it)
+        *reinterpret_cast<uint4 *>(&cmd[ms][lt][0]) = make_uint4(w0, cur.w, (uint32_t)legal, cmd_pack_w3(legal, a));
       }
       s += two ? 2 : 1;
       if (c.lane == 0) fs_flag_write(&posted, s);
@@ -360,17 +354,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       if (i + 2 < LP) ld_issue(i + 2);
     }
     FS_STAMP(8);
-    // The 32 legal-mask rows of a slot are 1216 contiguous bytes = 76 chunks of 16 B: lane l writes chunk l, lanes < 12
-    // also chunk 64 + l.  A chunk holds the bytes of table ta (from action `off` on) and possibly of ta + 1.
-    uint32_t ta[2], tb[2], off[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const uint32_t cidx = (uint32_t)c.lane + 64u * (uint32_t)q;
-      const uint32_t byte0 = 16u * ((cidx < 76u) ? cidx : 75u);
-      ta[q] = byte0 / BRL_NUM_ACTIONS;
-      off[q] = byte0 - ta[q] * BRL_NUM_ACTIONS;
-      tb[q] = (ta[q] + 1u < (uint32_t)TPB) ? ta[q] + 1u : ta[q];
-    }
+    const MaskChunk mc[2] = {make_mask_chunk((uint32_t)c.lane, TPB), make_mask_chunk((uint32_t)c.lane + 64u, TPB)};
     uint8_t *mrow = A.out.legal_action_mask + table0 * BRL_NUM_ACTIONS;
     const int64_t mstep = A.n * BRL_NUM_ACTIONS;
     int avail = 0;
@@ -383,14 +367,8 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
 #pragma unroll
       for (int q = 0; q < 2; q++) {
         if (q == 1 && c.lane >= 12) break;
-        const uint64_t la = *reinterpret_cast<const uint64_t *>(&cs[ta[q]][2]) & ALL_ACTIONS;
-        const uint64_t lb = *reinterpret_cast<const uint64_t *>(&cs[tb[q]][2]) & ALL_ACTIONS;
-        const uint32_t bits16 = (uint32_t)((la >> off[q]) | (lb << (BRL_NUM_ACTIONS - off[q])));
-        uint32_t d[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) d[i] = __umul24((bits16 >> (4 * i)) & 0xFu, 0x204081u) & 0x01010101u;
         // (write-through: -1.6 us against plain stores, see fs_store_wt; non-temporal: +1.0 us)
-        store_wt16(dstrow + 16 * (c.lane + 64 * q), brl_u32x4{d[0], d[1], d[2], d[3]});
+        store_wt16(dstrow + 16 * (c.lane + 64 * q), mask_chunk_bytes(cs, mc[q]));
       }
     }
   } else if (wave == 2) {
@@ -413,25 +391,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       }
       const uint4 w = wn;
       if (s + 1 < avail) wn = *reinterpret_cast<const uint4 *>(&cmd[s + 1][tl][0]);  // (uniform) next command, off the chain
-      const int a = (int)((w.w >> 8) & 63u);
-      const int seat = (int)((w.x >> 21) & 3u);
-      ts.sc = w.y;
-      // the acting player (src/roll_out.py:72), its action, n_legal
-      uint32_t info = (uint32_t)player_at(ts, seat) | ((uint32_t)a << 2) | (((w.x >> 23) & 63u) << 8);
-      note_first_denomination(ts.fd, seat, a);
-      const bool fin = mine && bits(ts.sc, SC_TERM, 1);
-      const uint64_t fm = __ballot(fin);
-      if (fm) {  // queue the finished boards, compacted over the tables: one lane per board in scorer B
-        if (fin) {
-          const int pos = nev + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-          *reinterpret_cast<uint4 *>(&evq[pos][0]) = make_uint4(ts.sc, ts.fd, (uint32_t)(s - 1) | ((uint32_t)tl << 8), vslot);
-          info |= 1u << 14;  // done (G2)
-        }
-        nev += __popcll(fm);
-      }
-      const bool dealt = (w.x & 0x200u) != 0u;  // re-dealt: no strain named yet; DDS values stay in the ring entry
-      vslot = dealt ? ((w.x >> 16) & 15u) : vslot;
-      ts.fd = dealt ? 0u : ts.fd;
+      const uint32_t info = scorer_follow(ts, vslot, nev, w, mine, (uint32_t)(s - 1), (uint32_t)tl, evq);
       if (mine) {
         minfo[s - 1][tl] = info;
         if (s == total) *reinterpret_cast<uint2 *>(&last_rw[tl][0]) = make_uint2(ts.fd, vslot);  // for B's write-back
@@ -459,19 +419,9 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
         const int e = e0 + c.lane;
         if (e < evs) {
           const uint4 q = *reinterpret_cast<const uint4 *>(&evq[e][0]);
-          const uint32_t tt = (q.z >> 8) & 63u, sl = q.z & 0xFFu;
-          Tbl tb;
-          tb.sc = q.x; tb.fd = q.y;
-          if (q.w != NO_SLOT) {  // a board dealt in this launch: DDS values from its ring entry
-            const uint4 vv = *reinterpret_cast<const uint4 *>(&ring[tt][q.w][8]);
-            pack_tricks(tb, vv.x, vv.y, vv.z, vv.w);
-          } else {  // the board the table came in with: its tricks are in the packed image
-            const uint2 *ip = reinterpret_cast<const uint2 *>(img + tt * TABLE_BYTES);
-            const uint2 tr = ip[W_TR], fdw = ip[W_FD];
-            tb.t0 = tr.x; tb.t1 = tr.y; tb.t2 = fdw.y;
-          }
-          terminal_reward(tb);  // A4
-          const int actor = (int)(minfo[sl][tt] & 3u);
+          const uint32_t tt = ev_table(q), sl = ev_step(q);
+          const Tbl tb = score_finished_board(q, ring[tt], img + tt * TABLE_BYTES);
+          const int actor = (int)info_actor(minfo[sl][tt]);
           frew[sl][tt] = (float)reward_of(tb, actor) / A.reward_scale;  // G1, src/roll_out.py:90
           if ((int)sl == total - 1) *reinterpret_cast<uint2 *>(&last_rw[tt][2]) = make_uint2(tb.r01, tb.r23);
         }
@@ -493,22 +443,15 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
         wave_lds_order();
         if (A.gae_adv != nullptr && c1 == total && c.lane == 0) fs_flag_write(&gae_ready, 1);
         if (q < m) {
-          const uint32_t inf[4] = {info4.x, info4.y, info4.z, info4.w};
-          float lgp[4];
-          uint32_t act[4], dn = 0;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            lgp[k] = s_neglog[(inf[k] >> 8) & 63u];
-            act[k] = (inf[k] >> 2) & 63u;
-            const uint32_t done = (inf[k] >> 14) & 1u;
-            dn |= done << (8 * k);
-            tcount += done;
-          }
+          brl_u32x4 act;
+          float4 lgp;
+          uint32_t dn;
+          tcount += unpack_info4(info4, s_neglog, act, lgp, dn);
           const int64_t rw = (int64_t)(b0 + q) * A.n + table0 + t4;
-          store_wt16(A.out.action + rw, brl_u32x4{act[0], act[1], act[2], act[3]});
+          store_wt16(A.out.action + rw, act);
           store_wt16(A.out.value + rw, brl_u32x4{0u, 0u, 0u, 0u});
           store_wt16(A.out.reward + rw, brl_u32x4{__float_as_uint(rew.x), __float_as_uint(rew.y), __float_as_uint(rew.z), __float_as_uint(rew.w)});
-          store_wt16(A.out.log_prob + rw, brl_u32x4{__float_as_uint(lgp[0]), __float_as_uint(lgp[1]), __float_as_uint(lgp[2]), __float_as_uint(lgp[3])});
+          store_wt16(A.out.log_prob + rw, brl_u32x4{__float_as_uint(lgp.x), __float_as_uint(lgp.y), __float_as_uint(lgp.z), __float_as_uint(lgp.w)});
           *reinterpret_cast<uint32_t *>(A.out.done + rw) = dn;  // G2 (4-byte pieces: plain; write-through no faster)
         }
       }
@@ -516,17 +459,11 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       if ((b0 & 7) == 0) FS_STAMP(b0 >> 3);
     }
     if (A.gae_adv != nullptr && total == 0 && c.lane == 0) fs_flag_write(&gae_ready, 1);  // (nothing to scan)
-    if (A.terminated_count != nullptr) {  // src/roll_out.py:85
-      uint32_t v = tcount;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-#ifndef BRL_TIMING
-      if (c.lane == 0 && v) atomicAdd(A.terminated_count, (unsigned long long)v);
-#endif
-    }
+    add_terminated(A.terminated_count, tcount, c.lane);
     if (total > 0 && c.lane < TPB) {
       // scalar words of the table's final state: first denominations and the DDS values of its current board (scorer A
       // left fd and the ring entry), rewards of the last macro-step (src/utils.py:126): its board's, or zero
+      // (its own text, not board_tricks: rereading a came-in-with board's tricks cost 0.27 us per launch, profiles/rollout_roles)
       const uint4 f = *reinterpret_cast<const uint4 *>(&last_rw[tl][0]);
       uint2 *p = reinterpret_cast<uint2 *>(img + tl * TABLE_BYTES);
       if (f.y != NO_SLOT) {
@@ -583,37 +520,34 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       const uint32_t w0a = cs[4 * g + r][0], w0b = cs[4 * g + r + 2][0];
       const uint32_t wh = hsel ? w0b : w0a;
       // apply sub-step s-1 to the images: one history bit per observer, or a freshly dealt board
-      if (head && !(wh & 0x200u) && (wh & 0x1FFu)) {
-        const uint32_t hb = (wh & 0x1FFu) - 1u;
+      if (head && !cmd_deal(wh) && cmd_hist_bit1(wh)) {
+        const uint32_t hb = cmd_hist_bit1(wh) - 1u;
         const uint32_t bit = (hb & ~3u) | ((hb - ho) & 3u);
         atomicOr(oh + (bit >> 5), 1u << (bit & 31u));
       }
-      uint64_t dealm = __ballot(head && ho == 0u && (wh & 0x200u));
+      uint64_t dealm = __ballot(head && ho == 0u && cmd_deal(wh));
       while (dealm) {  // rare: ~1 table in 25 per sub-step
         const int l = __ffsll((unsigned long long)dealm) - 1;  // lanes 0, 4, 30, 34: rows 0, 2, 1, 3
         dealm &= dealm - 1ull;
         const int row = (l >= 30) ? 1 + ((l - 30) >> 2) * 2 : (l >> 2) * 2;
         const uint32_t wq = __builtin_amdgcn_readlane(wh, l);
-        const uint32_t *re = &ring[4 * g + row][(wq >> 16) & 15u][0];
+        const uint32_t *re = &ring[4 * g + row][cmd_ring_slot(wq)][0];
         const uint64_t H = *reinterpret_cast<const uint64_t *>(re + 2 * dl_o);
         const uint32_t v = (dl_q == 0) ? vul_nibble_sc(re[13], dl_o)
                                        : ((dl_q == 13) ? (uint32_t)(H << 8) : ((dl_q == 14) ? (uint32_t)(H >> 24) : 0u));
         if (active) oimg[4 * g + row][dl_o][dl_q] = v;
       }
       wave_lds_order();
-      const uint32_t v0 = *reinterpret_cast<const uint16_t *>(og + rd_off + (int)((w0a >> 10) & 3u) * 64);
-      const uint32_t v1 = *reinterpret_cast<const uint16_t *>(og + rd_off + 512 + (int)((w0b >> 10) & 3u) * 64);
+      const uint32_t v0 = *reinterpret_cast<const uint16_t *>(og + rd_off + (int)cmd_observer(w0a) * 64);
+      const uint32_t v1 = *reinterpret_cast<const uint16_t *>(og + rd_off + 512 + (int)cmd_observer(w0b) * 64);
       uint8_t *dst = (s < total) ? optr : ((A.last_obs != nullptr) ? A.last_obs + (table0 + 4 * g) * BRL_OBS_SIZE + 16 * L : nullptr);
       optr += ostep;
       if (active && dst != nullptr) {
 #pragma unroll
         for (int k = 0; k < 2; k++) {
           const uint32_t word = k ? v1 : v0;
-          brl_u32x4 d;
-          d.x = __umul24(word & 0xFu, 0x204081u) & 0x01010101u;
-          d.y = __umul24((word >> 4) & 0xFu, 0x204081u) & 0x01010101u;
-          d.z = __umul24((word >> 8) & 0xFu, 0x204081u) & 0x01010101u;
-          d.w = __umul24(word >> 12, 0x204081u) & 0x01010101u;
+          const brl_u32x4 d = {nibble_bytes(word & 0xFu), nibble_bytes((word >> 4) & 0xFu), nibble_bytes((word >> 8) & 0xFu),
+                               nibble_bytes(word >> 12)};
           if (!(FS_EXP & 8)) __builtin_nontemporal_store(d, reinterpret_cast<brl_u32x4 *>(dst + 960 * k));
           else if (d.x == 0x12345678u) __builtin_nontemporal_store(d, reinterpret_cast<brl_u32x4 *>(dst + 960 * k));  // timing experiment: no stores
         }

@@ -236,6 +236,84 @@ def test_host_mirror_of_the_one_launch_rollout_with_gae(dds):
         assert rs1[5] == rs2[5]
 
 
+def _rollout_with_columns(e, n, T, substeps, seed, draw_base, left_out=(), last_obs=True, count=True, gae=None):
+    """one brl_rollout_random (gae = (last_val, gamma, gamma_lambda): brl_rollout_random_gae) launch through _capi with the
+    Transition columns named in `left_out`, last_obs and terminated_count passed as NULL on request.  Every buffer starts
+    as 0xA5 bytes, so a column that is not written is not mistaken for one that is."""
+    import ctypes as C
+    from brl_amd import _capi
+    from brl_amd.bridge_bidding import State
+    from brl_amd.roll_out import alloc_transition
+    dev = e.device
+    st = e.init(seed, num_envs=n)
+    traj = alloc_transition(T, n, dev)
+    p = _capi.TransitionPtrs()
+    for f in _capi.TransitionPtrs._names:
+        getattr(traj, f).view(torch.uint8).fill_(0xA5)
+        setattr(p, f, None if f in left_out else getattr(traj, f).data_ptr())
+    lo = torch.full((n, 480), 0xA5, dtype=torch.uint8, device=dev)
+    lm = torch.full((n, 38), 0xA5, dtype=torch.uint8, device=dev)
+    tc = torch.zeros(1, dtype=torch.int64, device=dev)
+    out = {"traj": traj, "last_obs": lo, "last_mask": lm, "count": tc, "state": State(e, st.packed)}   # (no cached fields)
+    s = torch.cuda.current_stream().cuda_stream
+    lop, tcp = (lo.data_ptr() if last_obs else None), (tc.data_ptr() if count else None)
+    if gae is None:
+        _capi.check(_capi.lib().brl_rollout_random(e._h, st.packed.data_ptr(), n, T, substeps, draw_base, 7600.0, C.byref(p), lop,
+                                                   lm.data_ptr(), tcp, s))
+    else:
+        out["adv"], out["tgt"] = torch.empty((T, n), device=dev), torch.empty((T, n), device=dev)
+        _capi.check(_capi.lib().brl_rollout_random_gae(e._h, st.packed.data_ptr(), n, T, draw_base, 7600.0, C.byref(p), lop,
+                                                       lm.data_ptr(), tcp, gae[0].data_ptr(), gae[1], gae[2],
+                                                       out["adv"].data_ptr(), out["tgt"].data_ptr(), s))
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("ws", [None, "0"])
+@pytest.mark.parametrize("substeps", [1, 2])
+@pytest.mark.parametrize("n,T", [(96, 9), (33, 5)])   # whole workgroups (only the missing columns take it off the wide path); ragged
+def test_fused_rollout_with_transition_columns_left_out(dds, oracle, ws, substeps, n, T):
+    """include/brl_hip.h: any Transition pointer may be NULL.  obs / value / log_prob, last_obs and terminated_count left
+    out: the columns that remain, last_mask and the packed state equal the oracle's rollout and, byte for byte, an
+    all-columns run of the same library; nothing is written through the pointers that were not passed."""
+    e = make_env(dds, 4, ws)
+    left_out = ("obs", "value", "log_prob")
+    part = _rollout_with_columns(e, n, T, substeps, 11, 3, left_out=left_out, last_obs=False, count=False)
+    full = _rollout_with_columns(e, n, T, substeps, 11, 3)
+    ref = oracle.init_random(n, seed=11)
+    want = oracle.rollout_random(ref, T, seed=11, substeps=substeps, draw_base=3)
+    for name in ("legal_action_mask", "action", "done", "reward"):
+        g = to_np(getattr(part["traj"], name))
+        assert g.shape == want[name].shape and np.array_equal(g, want[name]), name
+        assert torch.equal(getattr(part["traj"], name), getattr(full["traj"], name)), name
+    for name in left_out:   # untouched here, written (and right) in the all-columns run
+        assert bool((getattr(part["traj"], name).view(torch.uint8) == 0xA5).all()), name
+        assert np.array_equal(to_np(getattr(full["traj"], name)), want[name]), name
+    assert bool((part["last_obs"] == 0xA5).all()) and int(part["count"].item()) == 0
+    assert np.array_equal(to_np(full["last_obs"]), ref["observation"]) and int(full["count"].item()) == want["terminated_count"]
+    assert np.array_equal(to_np(part["last_mask"]), ref["legal_action_mask"]) and torch.equal(part["last_mask"], full["last_mask"])
+    assert torch.equal(part["state"].packed, full["state"].packed)
+    assert_state_equal(part["state"], ref, where=f"columns left out, ws={ws} sub={substeps} n={n}")
+
+
+def test_rollout_random_gae_with_columns_left_out(dds, oracle):
+    """brl_rollout_random_gae without obs / log_prob is the rollout launch followed by the scan of its columns: advantages and
+    targets equal the oracle's scan of the oracle's rollout."""
+    n, T, gamma, lam = 64, 7, 0.99, 0.9
+    e = make_env(dds, 4)
+    last_val = torch.from_numpy(np.random.default_rng(5).standard_normal(n).astype(np.float32)).to(e.device)
+    gl = float(torch.tensor(gamma * lam, dtype=torch.float32))
+    got = _rollout_with_columns(e, n, T, 1, 11, 3, left_out=("obs", "log_prob"), gae=(last_val, gamma, gl))
+    ref = oracle.init_random(n, seed=11)
+    want = oracle.rollout_random(ref, T, seed=11, draw_base=3)
+    for name in ("legal_action_mask", "action", "done", "value", "reward"):
+        assert np.array_equal(to_np(getattr(got["traj"], name)), want[name]), name
+    want_adv, want_tgt = oracle.gae(want["done"], want["value"], want["reward"], to_np(last_val), gamma, lam)
+    assert np.array_equal(to_np(got["adv"]), want_adv) and np.array_equal(to_np(got["tgt"]), want_tgt)
+    assert np.array_equal(to_np(got["last_obs"]), ref["observation"]) and int(got["count"].item()) == want["terminated_count"]
+    assert_state_equal(got["state"], ref, where="gae with columns left out")
+
+
 def test_gae_bit_exact(env, oracle):
     from brl_amd.gae import gae_scan
     rng = np.random.default_rng(2)
