@@ -1,6 +1,7 @@
 """-m gpu: the batched league evaluation (brl_amd/league.py, csrc/brl_league.hip) — the route against its numpy restatement, the
 grouped forward against brl_mlp_forward_rows (bit for bit) and float64, whole leagues replayed through the CPU oracle match by
 match, batching, the mirror property, PFSP's league under the trainer and both command lines."""
+import copy
 import glob
 import os
 import subprocess
@@ -63,7 +64,10 @@ def test_route_equals_the_numpy_restatement(P, n, team):
 
 
 def _nets(fp, seeds):
-    return [fp.init(s, device="cuda") for s in seeds]
+    """one network per seed, every parameter perturbed with a seed of its own (tests/nets.py): on hk.Linear's zero biases a forward
+    that read another network's or another layer's bias would give the same numbers"""
+    from tests.nets import perturbed
+    return [perturbed(fp.init(s, device="cuda"), 1000 + s) for s in seeds]
 
 
 def _table(refs):
@@ -119,7 +123,8 @@ def test_grouped_forward_equals_forward_rows_bit_for_bit(activation, model, M, s
         if sizes[k] == 0:
             continue
         idx = rows[int(gf[k]):int(gf[k + 1])][:64]
-        net64 = fp.init(11 + k).double()
+        net64 = copy.deepcopy(nets[k]).double().cpu()
+        assert float(net64.body[0].bias.abs().min()) > 0 and (M == 1 or not torch.equal(net64.critic.bias, nets[(k + 1) % M].critic.bias.double().cpu()))
         with torch.no_grad():
             logits, value = net64(obs[idx].cpu().double())
         got = out[idx].cpu().double()

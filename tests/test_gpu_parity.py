@@ -2945,8 +2945,9 @@ def test_inference_snapshot_large_batch_paths_against_float64(model, monkeypatch
     library's exact fp32 GEMM (inference_gemm = "library") — through the WHOLE network (src/models.py:23-33) against the module in float64:
     the two bf16x3 paths are no further from float64 than the library path (fp32-grade end to end), and follow refreshed weights."""
     from brl_amd.models import InferenceSnapshot, make_forward_pass
+    from tests.nets import perturbed
     fp = make_forward_pass("relu", model)
-    net = fp.init(11, device="cuda")
+    net = perturbed(fp.init(11, device="cuda"), 21)     # (no bias is hk.Linear's zero: tests/nets.py)
     g = torch.Generator(device="cuda").manual_seed(5)
     obs = torch.rand((8192, 480), device="cuda", generator=g) < 0.12
     with torch.no_grad():
@@ -2970,8 +2971,7 @@ def test_inference_snapshot_large_batch_paths_against_float64(model, monkeypatch
     # new weights: refresh re-splits the planes INTO the same tensors (their addresses sit in captured graphs)
     ptrs = [w.data_ptr() for w in snap_p.wp]
     with torch.no_grad():
-        for p_ in net.parameters():
-            p_.mul_(1.01)
+        perturbed(net, 29)                              # (a second perturbation: scaling would leave a zero bias zero)
         snap_p.refresh(net)
         ref.load_state_dict({k: t.double().cpu() for k, t in net.state_dict().items()})
         lg64, v64 = ref(obs.double().cpu())
@@ -3039,8 +3039,10 @@ def test_mlp_forward_rows_matches_float64(activation, model, n, m):
     from brl_amd import _capi
     from brl_amd.evaluation import _Forward
     from brl_amd.models import make_forward_pass
+    from tests.nets import perturbed
     fp = make_forward_pass(activation, model)
-    net = fp.init(7, device="cuda")
+    net = perturbed(fp.init(7, device="cuda"), 40 + m)    # (no bias is hk.Linear's zero: tests/nets.py)
+    state = {k: t.cpu() for k, t in net.state_dict().items()}
     g = torch.Generator(device="cuda").manual_seed(n + m)
     obs = torch.rand(n, 480, device="cuda", generator=g) < 0.1
     rows = torch.randperm(n, device="cuda", generator=g)[:m].contiguous() if m <= n else None
@@ -3050,6 +3052,8 @@ def test_mlp_forward_rows_matches_float64(activation, model, n, m):
     fwd.rows(obs, rows, m, out, None)
     torch.cuda.synchronize()
     net64 = fp.init(7).double()
+    net64.load_state_dict({k: t.double() for k, t in state.items()})
+    assert float(net64.body[0].bias.abs().min()) > 0
     with torch.no_grad():
         logits, value = net64(obs[rows].cpu().double())
     got = out[rows].cpu().double()
@@ -3066,6 +3070,7 @@ def test_mlp_forward_rows_matches_float64(activation, model, n, m):
     from oracle.binding import shim_path
     shim = C.CDLL(shim_path())
     cpu = fp.init(7)
+    cpu.load_state_dict(state)
     r = _capi.MlpRef()
     r.nlayers, r.act, r.in_features, r.hidden = len(cpu.body), 0 if activation == "relu" else 1, 480, 1024
     for i, lin in enumerate(cpu.body):

@@ -39,6 +39,52 @@ CASES = {
 }
 
 
+DEEPMIND_PERTURB_SEED = 22
+# the seed of a case's batches (step t draws fake_batch(1, B, seed + t)): 200 unless that misses a cap of the input conditions
+DEEPMIND_BATCH_SEEDS = {}
+DEEPMIND_GATE_BAND = 4e-6   # of |h| |W| + |b|: the fp32 products' rounding band of a ReLU pre-activation
+
+
+def deepmind_case(case, device):
+    """-> (activation, model, B, cfg, seed of its batches, forward pass, its network on `device`): `init(4)` with N(0, 0.01) added to
+    every weight and N(0, 0.1) to every bias, as `fair_case` — at hk.Linear's zero biases the step's first forward adds no bias at
+    all and the later ones biases of magnitude lr.  (Drawn on the host, so the CPU check of the cases' inputs sees the same network.)"""
+    from brl_amd.models import make_forward_pass
+    from tests.nets import perturbed
+    from tests.test_update_cpu import CFG
+    activation, model, B, over = CASES[case]
+    cfg = dict(CFG, lr=LR, minibatch_size=B, update_epochs=1, graph_update=True, **over)
+    fp = make_forward_pass(activation, model)
+    net = perturbed(fp.init(4), DEEPMIND_PERTURB_SEED)
+    return activation, model, B, cfg, DEEPMIND_BATCH_SEEDS.get(case, 200), fp, net.to(device)
+
+
+def deepmind_gate_fn(P, stored, ambiguous):
+    """a gate_fn for tests/ppo_numpy.forward: z > 0, except where |z| is within DEEPMIND_GATE_BAND of the magnitude sum behind it —
+    there the gate is stored[k] (the fp32 step's own; None: z > 0 all the same) and ambiguous[0] counts the entry"""
+    def gate_fn(k, z, h_in):
+        band = DEEPMIND_GATE_BAND * (np.abs(h_in) @ np.abs(P[k][0]).T + np.abs(P[k][1]))
+        amb = np.abs(z) < band
+        gate = z > 0
+        if amb.any():
+            ambiguous[0] += int(amb.sum())
+            if stored is not None:
+                gate[amb] = stored[k][amb]
+        return gate
+    return gate_fn
+
+
+def deepmind_input_conditions(cfg, P, args, activation, stored=None):
+    """the two conditions on a step's INPUTS, from float64 alone where stored is None -> (ambiguous ReLU entries, samples at the
+    ratio kink, samples at the value kink, the gate_fn for the gradient pass with its counter)"""
+    from tests.ppo_numpy import forward
+    ambiguous = [0]
+    gate_fn = deepmind_gate_fn(P, stored, ambiguous) if activation == "relu" else None
+    logits, value, _, _, _ = forward(P, args[0].astype(np.float64), activation, gate_fn)
+    n_ratio, n_value = _ppo_kinks(cfg, logits, value, args[1].astype(bool), args[2], args[3], args[4])
+    return ambiguous[0], n_ratio, n_value, gate_fn, ambiguous
+
+
 def _np(t):
     return t.detach().cpu().double().numpy()
 
@@ -59,7 +105,8 @@ def _ppo_kinks(cfg, logits, value, mask, action, old_value, old_lp, rel=1e-5):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_fused_deepmind_step_matches_float64(case):
-    """Three successive update_step calls, each ONE minibatch step (batch = minibatch, update_epochs = 1), through FusedMinibatch; the
+    """Three successive update_step calls, each ONE minibatch step (batch = minibatch, update_epochs = 1), through FusedMinibatch, from
+    a network whose every parameter is perturbed (deepmind_case: no bias is hk.Linear's zero, at the first step either); the
     float64 reference of step t starts from the GPU's own parameters and moments before it (copied to the host), so errors do not
     build up.  After each call:
       * the five logged losses within 2e-5 of float64 (with the illegal-action term the total also carries the fp32 Gram's 2e-6 relative
@@ -75,22 +122,19 @@ def test_fused_deepmind_step_matches_float64(case):
         (fp32 rounding of v).
     ReLU gates: where a float64 pre-activation is within 4e-6 of its |h||W| + |b| sum (the fp32 products' rounding) of 0, the gate is the
     step's own (fm.hs[l] > 0, rows in the step's permuted order); such entries must be fewer than 1e-4 of all.  Samples at PPO's clip
-    kinks (ratio at 1 +- clip_eps, value change at clip_eps, within 1e-5) are counted: at most 2 per step."""
-    from brl_amd.models import make_forward_pass
+    kinks (ratio at 1 +- clip_eps, value change at clip_eps, within 1e-5) are counted: at most 2 per step — conditions on the inputs,
+    which tests/test_update_cpu.py checks for every case's seeds without a GPU."""
     from brl_amd.roll_out import Transition
     from brl_amd.update import FusedMinibatch, make_optimizer, make_update_step
-    from tests.ppo_numpy import adam_step, forward, loss_and_grads, params_of
-    from tests.test_update_cpu import CFG, fake_batch
-    activation, model, B, over = CASES[case]
-    cfg = dict(CFG, lr=LR, minibatch_size=B, update_epochs=1, graph_update=True, **over)
-    fp = make_forward_pass(activation, model)
-    net = fp.init(4, device="cuda")
+    from tests.ppo_numpy import adam_step, loss_and_grads, params_of
+    from tests.test_update_cpu import fake_batch
+    activation, model, B, cfg, seed, fp, net = deepmind_case(case, "cuda")
     opt_state = make_optimizer(cfg, net)
     rs = (net, opt_state, None, None, 0, 9)
     nl = len(net.body)
     upd = make_update_step(cfg, fp)
     for t in (1, 2, 3):
-        tb, adv, tgt = fake_batch(1, B, seed=200 + t)
+        tb, adv, tgt = fake_batch(1, B, seed=seed + t)
         lr_t = LR * (1.0 - (t - 1) / cfg["num_updates"]) if cfg.get("anneal_lr") else LR
         assert abs(opt_state["opt"].param_groups[0]["lr"] - lr_t) < 1e-12
         P = params_of(net)
@@ -118,20 +162,8 @@ def test_fused_deepmind_step_matches_float64(case):
         flat = Transition(*[x.reshape((B,) + x.shape[2:])[perm] for x in tb])
         args = (flat.obs.numpy(), flat.legal_action_mask.numpy(), flat.action.numpy().astype(np.int64), flat.value.double().numpy(),
                 flat.log_prob.double().numpy(), adv.reshape(-1)[perm].double().numpy(), tgt.reshape(-1)[perm].double().numpy())
-        gate_fn, ambiguous = None, [0]
-        if activation == "relu":
-            hs_gpu = [(fm.hs[l] > 0).cpu().numpy() for l in range(nl)]
-
-            def gate_fn(k, z, h_in, P=P, hs_gpu=hs_gpu):
-                band = 4e-6 * (np.abs(h_in) @ np.abs(P[k][0]).T + np.abs(P[k][1]))
-                amb = np.abs(z) < band
-                gate = z > 0
-                if amb.any():
-                    gate[amb] = hs_gpu[k][amb]
-                    ambiguous[0] += int(amb.sum())
-                return gate
-        logits, value, _, _, _ = forward(P, args[0].astype(np.float64), activation, gate_fn)
-        n_ratio, n_value = _ppo_kinks(cfg, logits, value, args[1].astype(bool), args[2], args[3], args[4])
+        stored = [(fm.hs[l] > 0).cpu().numpy() for l in range(nl)] if activation == "relu" else None
+        _, n_ratio, n_value, gate_fn, ambiguous = deepmind_input_conditions(cfg, P, args, activation, stored)
         assert n_ratio <= 2 and n_value <= 2, (t, n_ratio, n_value)
         ambiguous[0] = 0
         want_total, want_aux, G = loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
@@ -198,15 +230,12 @@ def fair_case(case, device):
     added to every weight and N(0, 0.1) to every bias — under ReLU too: hk.Linear's zero biases would hide a bias the step never
     adds, or adds from the wrong layer.  (Drawn on the host, so the CPU check of the cases' inputs sees the same network.)"""
     from brl_amd.models import make_forward_pass
+    from tests.nets import perturbed
     from tests.test_update_cpu import CFG
     activation, B, over, path, seed = FAIR_CASES[case]
     cfg = dict(CFG, lr=LR, minibatch_size=B, update_epochs=1, graph_update=True, **over)
     fp = make_forward_pass(activation, "FAIR")
-    net = fp.init(4)
-    gen = torch.Generator().manual_seed(FAIR_PERTURB_SEED)
-    with torch.no_grad():
-        for q in net.parameters():
-            q.add_(torch.randn(q.shape, generator=gen) * (0.1 if q.dim() == 1 else 0.01))
+    net = perturbed(fp.init(4), FAIR_PERTURB_SEED)
     return activation, B, cfg, path, seed, fp, net.to(device)
 
 

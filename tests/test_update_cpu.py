@@ -194,11 +194,13 @@ def test_allreduce_is_noop_without_process_group():
 
 def test_inference_snapshot_matches_module_cpu():
     """models.InferenceSnapshot (fused bias+ReLU epilogue, merged heads) == the module's own forward; refresh()
-    re-reads updated weights into the same tensors (their addresses are baked into captured graphs)."""
+    re-reads updated weights into the same tensors (their addresses are baked into captured graphs).  On a network whose biases
+    are not hk.Linear's zeros, "updated" by a second perturbation (scaling would leave a zero bias zero)."""
     import torch
     from brl_amd.models import InferenceSnapshot, make_forward_pass
+    from tests.nets import perturbed
     fp = make_forward_pass("relu", "DeepMind")
-    net = fp.init(5)
+    net = perturbed(fp.init(5), 31)
     x = (torch.rand(64, 480) < 0.1)
     snap = InferenceSnapshot.make(net)
     assert snap is not None
@@ -209,12 +211,12 @@ def test_inference_snapshot_matches_module_cpu():
     assert torch.allclose(lg, lg2, atol=1e-5) and torch.allclose(v, v2, atol=1e-5)
     ptrs = [w.data_ptr() for w, _ in snap.body] + [snap.head_w.data_ptr()]
     with torch.no_grad():
-        for p in net.parameters():
-            p.mul_(0.5)
+        perturbed(net, 32)
         snap.refresh(net)
         lg3, v3 = net(x.float())
         lg4, v4 = snap(x)
     assert torch.allclose(lg3, lg4, atol=1e-5) and torch.allclose(v3, v4, atol=1e-5)
+    assert float((lg3 - lg).abs().max()) > 1e-2 and float((v3 - v).abs().max()) > 1e-2     # (the update did move the outputs)
     assert ptrs == [w.data_ptr() for w, _ in snap.body] + [snap.head_w.data_ptr()]
     assert InferenceSnapshot.make(make_forward_pass("relu", "FAIR").init(0)) is None  # not covered: callers fall back
 
@@ -252,11 +254,9 @@ def _batch64(B, seed):
 
 
 def _perturb(net, seed):
-    """hk.Linear's zero biases would hide a bias mix-up: every parameter moved a little"""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for q in net.parameters():
-            q.add_(torch.randn(q.shape, generator=g, dtype=q.dtype) * (0.1 if q.dim() == 1 else 0.01))
+    """hk.Linear's zero biases would hide a bias mix-up: every parameter moved a little (tests/nets.py)"""
+    from tests.nets import perturbed
+    perturbed(net, seed)
 
 
 # the switches of the PPO step (src/update.py): each one changes the loss or its gradient
@@ -399,6 +399,37 @@ def test_fair_float64_cases_meet_their_input_conditions(case):
         assert n_ratio <= KINK_CAP and n_value <= KINK_CAP, (t, n_ratio, n_value)
         assert n_amb <= AMBIGUOUS_CAP * B * len(FAIR_SITES) * P[0][0].shape[0], (t, n_amb)
         _, _, G = fair_loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
+        P, M, V, _ = adam_step(cfg, t, P, M, V, G, lr=lr_t)
+        P = [tuple(x.astype(np.float32).astype(np.float64) for x in pair) for pair in P]
+
+
+def _deepmind_case_names():
+    from tests.test_gpu_update_float64 import CASES
+    return list(CASES)
+
+
+@pytest.mark.parametrize("case", _deepmind_case_names())
+def test_deepmind_float64_cases_meet_their_input_conditions(case):
+    """The twin of test_fair_float64_cases_meet_their_input_conditions for tests/test_gpu_update_float64.test_fused_deepmind_step_matches_float64,
+    whose cases start from a perturbed network (deepmind_case): per step, the ReLU pre-activations inside their fp32 rounding band at
+    most 1e-4 of all, the samples at PPO's clip kinks at most 2 of each kind — in float64 alone, z > 0 in place of the stored gates,
+    the parameters of steps 2 and 3 from the float64 Adam step rounded to fp32.  A seed that misses a cap is changed in
+    DEEPMIND_BATCH_SEEDS, never the cap."""
+    from tests.ppo_numpy import adam_step, loss_and_grads, params_of
+    from tests.test_gpu_update_float64 import AMBIGUOUS_CAP, KINK_CAP, LR, deepmind_case, deepmind_input_conditions
+    activation, _, B, cfg, seed, _, net = deepmind_case(case, "cpu")
+    P = params_of(net)
+    nl, H = len(P) - 2, P[0][0].shape[0]
+    assert all(np.abs(b).min() > 0 for _, b in P)
+    M = [(np.zeros_like(W), np.zeros_like(b)) for W, b in P]
+    V = [(np.zeros_like(W), np.zeros_like(b)) for W, b in P]
+    for t in (1, 2, 3):
+        _, _, _, _, args = _batch64(B, seed=seed + t)
+        lr_t = LR * (1.0 - (t - 1) / cfg["num_updates"]) if cfg.get("anneal_lr") else LR
+        n_amb, n_ratio, n_value, gate_fn, _ = deepmind_input_conditions(cfg, P, args, activation)
+        assert n_ratio <= KINK_CAP and n_value <= KINK_CAP, (t, n_ratio, n_value)
+        assert n_amb <= AMBIGUOUS_CAP * B * H * nl, (t, n_amb)
+        _, _, G = loss_and_grads(cfg, P, *args, activation=activation, gate_fn=gate_fn)
         P, M, V, _ = adam_step(cfg, t, P, M, V, G, lr=lr_t)
         P = [tuple(x.astype(np.float32).astype(np.float64) for x in pair) for pair in P]
 
