@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "nan_math.hpp"
+
 struct AdamRange {
   float *p;
   const float *g;
@@ -41,8 +43,9 @@ __device__ __forceinline__ void adam_range_block(const AdamRange &A, const int b
     __syncthreads();
     if (tid == 0) {
       const float norm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-      // torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to 1
-      red[4] = (A.max_norm > 0.0f) ? fminf(A.max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
+      // torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to 1 (torch.clamp: a NaN norm gives a NaN
+      // coefficient and every parameter goes NaN; fminf would return 1 and apply the step unclipped)
+      red[4] = (A.max_norm > 0.0f) ? min_nan(A.max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
       if (b == 0 && A.norm_out) *A.norm_out = norm;
     }
     __syncthreads();

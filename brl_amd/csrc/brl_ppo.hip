@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "abi_common.hpp"
+#include "nan_math.hpp"   // clamp_nan / min_nan / max_nan: `_loss_fn`'s clip, minimum and maximum keep a NaN
 
 static inline unsigned thread_grid(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
@@ -102,8 +103,8 @@ __device__ __forceinline__ void ppo_loss_sample(const PpoArgs &A, const PpoSampl
   const float logratio = lp - S.old_logp;
   const float ratio = expf(logratio);
   const float eps = A.clip_eps;
-  const float a1 = ratio * g, a2 = fminf(fmaxf(ratio, 1.0f - eps), 1.0f + eps) * g;
-  const float la = -fminf(a1, a2);
+  const float a1 = ratio * g, a2 = clamp_nan(ratio, 1.0f - eps, 1.0f + eps) * g;
+  const float la = -min_nan(a1, a2);
   const bool inside = (ratio >= 1.0f - eps) && (ratio <= 1.0f + eps);
   const float dratio = ((a1 < a2) || inside) ? -g : 0.0f;  // d(-min(a1, a2)) / d ratio (ties: both branches agree)
   const float dlp = dratio * ratio * invB;
@@ -111,18 +112,19 @@ __device__ __forceinline__ void ppo_loss_sample(const PpoArgs &A, const PpoSampl
   const float ov = S.old_value, t = S.tgt;
   float vl, dv;
   if (A.value_clipping) {
-    const float dcl = fminf(fmaxf(v - ov, -eps), eps);
+    const float dcl = clamp_nan(v - ov, -eps, eps);
     const float vc = ov + dcl;
     const float l1 = (v - t) * (v - t), l2 = (vc - t) * (vc - t);
-    vl = 0.5f * fmaxf(l1, l2);
+    vl = 0.5f * max_nan(l1, l2);
     const bool unclipped = (v - ov >= -eps) && (v - ov <= eps);
-    dv = (l1 >= l2) ? (v - t) : (unclipped ? (vc - t) : 0.0f);
+    const float dc = vc - t, dc0 = dc - dc;   // dc0: +0, or NaN where dc is not finite = (vc - t) * 0 of the reference's clipped branch
+    dv = (l1 >= l2) ? (v - t) : (unclipped ? dc : dc0);
   } else {
     vl = 0.5f * (v - t) * (v - t);
     dv = v - t;
   }
   // entropy of the masked policy, 0 log 0 = 0 (distrax)
-  const float H = -wave_sum_f((legal && p > 0.0f) ? p * lsm : 0.0f);
+  const float H = -wave_sum_f((legal && !(p <= 0.0f)) ? p * lsm : 0.0f);   // (!(p <= 0): a NaN probability stays in the sum)
   const float dH = legal ? -p * (lsm + H) : 0.0f;
   const float onehot = (lane == act) ? 1.0f : 0.0f;
   const bool live = A.masked ? legal : in;
@@ -220,8 +222,9 @@ __global__ __launch_bounds__(512) void k_ppo_stats(const float *partials, int64_
     const float vi = (lane < D) ? vec[lane] : 0.0f;
     const float num = wave_sum_f(vi * gv), den = wave_sum_f(vi * vi);
     if (lane == 0) {
-      out[6] = 0.5f * sqrtf(fmaxf(num / fmaxf(den, 1.17549435e-38f), 0.0f));
-      out[0] = st[1] + vf_coef * st[0] - ent_coef * st[2];
+      const float ray = num / fmaxf(den, 1.17549435e-38f);
+      out[6] = 0.5f * sqrtf(max_nan(ray, 0.0f));   // (a NaN Gram matrix gives a NaN norm)
+      out[0] = (st[1] + vf_coef * st[0] - ent_coef * st[2]) + 0.0f * out[6];   // (src/update.py:146-151 with a zero coefficient: a NaN norm is a NaN total)
       out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[3]; out[5] = st[4];
       out[7] = 0.0f;
     }

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_sl_loss(const float *logits, i
       const bool legal = (lm >> j) & 1ull;
       const float lsm = (z - mx) - lse;
       const float p = legal ? expf(lsm) : 0.0f;
-      H -= (p > 0.0f) ? p * lsm : 0.0f;  // 0 log 0 = 0
+      H -= !(p <= 0.0f) ? p * lsm : 0.0f;  // 0 log 0 = 0 (!(p <= 0): a NaN probability stays in the sum)
       ill += legal ? 0.0f : expf((z - mx2) - lse2);
     }
     const float ly = (lg[y] - mx2) - lse2;

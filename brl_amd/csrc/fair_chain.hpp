@@ -19,6 +19,8 @@
 // Included by brl_ppo.hip after ppo_heads.hpp (wave_sum_f, dpp_move_f, PpoArgs, ppo_loss_sample, BiasSegs).
 #pragma once
 
+#include "nan_math.hpp"   // relu_nan
+
 #ifndef FAIR_EXP
 #define FAIR_EXP 0   // experiment builds (scripts/fair_chain_probe.py): 1 no MFMAs, 2 no weight loads, 4 no LDS fragment reads,
                      // 8 no global stores of activations / gradients, 16 filler jobs load real weights, 32 / 64 no backward / forward
@@ -67,7 +69,7 @@ struct Args {
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 __device__ __forceinline__ f32x4 act4(f32x4 v, int act) {
-  if (act == 0) return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+  if (act == 0) return f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};   // (a NaN stays NaN)
   return f32x4{tanhf(v.x), tanhf(v.y), tanhf(v.z), tanhf(v.w)};
 }
 // d * act'(.) from the activation's OUTPUT h: ReLU h > 0, tanh 1 - h^2 (src/models.py:16)

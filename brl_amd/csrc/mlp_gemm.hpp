@@ -22,6 +22,8 @@
 //     k_adam_norm in index order.
 #pragma once
 
+#include "nan_math.hpp"   // relu_nan: the ReLU epilogue keeps a NaN
+
 namespace mg {
 
 constexpr int BM = 64, BN = 64, BK = 32, THREADS = 256;
@@ -373,7 +375,7 @@ __device__ __forceinline__ void gemm_tile(const Args &G, float *lds, int bid, in
         const f32x4 bb = ebias[bj];
         if (relu) {
 #pragma unroll
-          for (int i = 0; i < 4; i++) v[i] = fmaxf(v[i] + bb[i], 0.0f);
+          for (int i = 0; i < 4; i++) v[i] = relu_nan(v[i] + bb[i]);
         } else {
 #pragma unroll
           for (int i = 0; i < 4; i++) v[i] = tanhf(v[i] + bb[i]);

@@ -356,7 +356,7 @@ __device__ __forceinline__ void gemm_tile(const Args &X, unsigned char *lds, int
       if (EPI == mg::EPI_BIAS_ACT) {
         if (relu) {
 #pragma unroll
-          for (int i = 0; i < 4; i++) o[i] = fmaxf(o[i] + bias4[i], 0.0f);
+          for (int i = 0; i < 4; i++) o[i] = relu_nan(o[i] + bias4[i]);
         } else {
 #pragma unroll
           for (int i = 0; i < 4; i++) o[i] = tanhf(o[i] + bias4[i]);

@@ -24,6 +24,8 @@
 // Included by brl_infer16.hip.
 #pragma once
 
+#include "nan_math.hpp"   // relu_nan: the ReLU epilogue keeps a NaN
+
 namespace lin16 {
 
 constexpr int BM = 256, BN = 128, BK = 64, STAGES = 3, THREADS = 512;
@@ -326,7 +328,7 @@ __device__ __forceinline__ void linear_tile(const Args &G, char *lds, float *bia
       if (hrow < 48) *reinterpret_cast<uint4 *>(lds + HW_OFF + hrow * C_ROW_BYTES + 16 * (tid & 15)) = hwv[u];
     }
   }
-  const float floor_v = G.relu ? 0.0f : -__builtin_inff();
+  const bool relu = G.relu != 0;
   // Two halves (mb = 0: tile rows 64 wm + 0..31, mb = 1: + 32..63): the second half is packed while the first half's stores are
   // on their way.  Raw barriers with lgkmcnt(0) only: __syncthreads() would also wait for those stores (vmcnt(0)).
 #pragma unroll
@@ -341,8 +343,10 @@ __device__ __forceinline__ void linear_tile(const Args &G, char *lds, float *bia
         f32x2 lo = {acc[mb][nb][4 * q + 0], acc[mb][nb][4 * q + 1]}, hi = {acc[mb][nb][4 * q + 2], acc[mb][nb][4 * q + 3]};
         lo = lo + f32x2{bv.x, bv.y};   // (v_pk_add_f32)
         hi = hi + f32x2{bv.z, bv.w};
-        lo.x = fmaxf(lo.x, floor_v); lo.y = fmaxf(lo.y, floor_v);
-        hi.x = fmaxf(hi.x, floor_v); hi.y = fmaxf(hi.y, floor_v);
+        if (relu) {   // (IEEE maximum, not fmaxf: a NaN stays NaN)
+          lo.x = relu_nan(lo.x); lo.y = relu_nan(lo.y);
+          hi.x = relu_nan(hi.x); hi.y = relu_nan(hi.y);
+        }
         uint2 pk;
         pk.x = pack2<FMT>(lo);
         pk.y = pack2<FMT>(hi);

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(THREADS) void k_linear_x3p(Args G) {
   LX3_STAMP(1);
   // ---- epilogue: lane holds, per block b, row m0 + 64 wm + 32 b + r32, columns n0 + 32 wn + 8 g + 4 hh + (0..3)
   __syncthreads();      // every wave is done with the stages (its last fragments are in registers; no DMA is in flight)
-  const float floor_v = G.relu ? 0.0f : -__builtin_inff();
+  const bool relu = G.relu != 0;
 #pragma unroll
   for (int b = 0; b < 2; b++) {
     const int row = 64 * wm + 32 * b + r32, em = m0 + row;
@@ -270,7 +270,10 @@ __global__ __launch_bounds__(THREADS) void k_linear_x3p(Args G) {
       const f32x4 bias4 = *reinterpret_cast<const f32x4 *>(G.bias + n0 + col);
       f32x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; e++) o[e] = fmaxf((acc[b][1][4 * g + e] + acc[b][0][4 * g + e]) + bias4[e], floor_v);
+      for (int e = 0; e < 4; e++) {
+        const float z = (acc[b][1][4 * g + e] + acc[b][0][4 * g + e]) + bias4[e];
+        o[e] = relu ? relu_nan(z) : z;     // (IEEE maximum, not fmaxf: a NaN stays NaN)
+      }
       if (G.y != nullptr && em < G.M) *reinterpret_cast<f32x4 *>(G.y + (int64_t)em * G.ldy + n0 + col) = o;
       if (G.yp != nullptr) {
         unsigned h[4], m[4], l[4];

@@ -15,6 +15,8 @@
 // Included by brl_ppo.hip after ppo_update.hpp.
 #pragma once
 
+#include "nan_math.hpp"   // max_nan
+
 constexpr int HD_ROWS = 4;     // samples per workgroup of k_heads_loss (of the 16 rows of an MFMA tile; see the kernel)
 constexpr int HD_WAVES = 8;    // waves per workgroup = K splits; waves 0..3 finish one sample each
 constexpr int HD_MAX_PARTS = 8;    // partial products k_heads_loss adds (k_heads_product: <= 8 K ranges)
@@ -373,7 +375,8 @@ __global__ __launch_bounds__(1024) void k_ppo_stats2(const float *partials, int6
     for (int k = 0; k < D; k++)
       gv += ((lane < D) ? g[k * D + lane] : 0.0f) * __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), k));
     const float num = wave_sum_f(v * gv), den = wave_sum_f(v * v);
-    const float sigma = sqrtf(fmaxf(num / fmaxf(den, 1.17549435e-38f), 0.0f));
+    const float ray = num / fmaxf(den, 1.17549435e-38f);
+    const float sigma = sqrtf(max_nan(ray, 0.0f));   // (a NaN Gram matrix gives a NaN norm)
     if (vec_out != nullptr && lane < D + 2) vec_out[lane] = (lane < D) ? v * (1.0f / sqrtf(fmaxf(den, 1.17549435e-38f))) : ((lane == D) ? sigma : 0.0f);
     if (lane == 0) {
       out[6] = 0.5f * sigma;

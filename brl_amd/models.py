@@ -121,7 +121,7 @@ class ActorCritic(nn.Module):
 
 class InferenceSnapshot:
     """Inference-only copy of a "DeepMind" ReLU ActorCritic (no autograd): weights transposed (and cast to `dtype`
-    when given) ONCE, bias + ReLU in the GEMM epilogue (``torch._addmm_activation`` -> hipBLASLt), the actor and
+    when given) ONCE, bias in the GEMM (``torch.addmm``) + ``relu_`` (which keeps a NaN; the library's fused ReLU epilogue does not), the actor and
     critic heads as one 39-row GEMM.  With a 16-bit `dtype` and a library handle (`env`) the hidden layers run on the
     library's own kernel instead (``brl_linear_act``) and ``head_parts`` lets the last layer's launch compute the heads'
     share (``brl_linear_act_heads``).  Build one per rollout / evaluation call — it does not follow later weight
@@ -327,9 +327,10 @@ class InferenceSnapshot:
             for (w, _), (wn, _) in zip(self.body, self.body_nk):
                 w.copy_(wn.t())
             self._body_stale = False
-        fused = hasattr(torch, "_addmm_activation")
+        # (addmm + relu_, not torch._addmm_activation: the library's fused ReLU epilogue is max(x, 0), which returns 0 for a NaN
+        #  pre-activation — a NaN weight would vanish behind the layer; relu_ keeps it.  DESIGN.md, "Non-finite values")
         for w, b in self.body:
-            x = torch._addmm_activation(b, x, w, use_gelu=False) if fused else torch.addmm(b, x, w).relu_()
+            x = torch.addmm(b, x, w).relu_()
         return x
 
     HEAD_PART_LD = 40

@@ -82,7 +82,7 @@ def ppo_loss(config, logits, value, batch: Transition, gae, targets):
     loss_actor = -torch.minimum(ratio * gae, ratio.clamp(1.0 - config["clip_eps"], 1.0 + config["clip_eps"]) * gae).mean()
     mlp = masked_log_softmax(logits, mask)
     p = mlp.exp()
-    entropy = -(torch.where(p > 0, p * mlp, torch.zeros_like(p))).sum(-1).mean()   # distrax: 0 log 0 = 0
+    entropy = -(torch.where(p == 0, torch.zeros_like(p), p * mlp)).sum(-1).mean()   # distrax: 0 log 0 = 0 (a NaN stays)
     # src/update.py:136-141: the L2 (spectral) norm of the illegal-action probabilities is always computed and
     # logged, whatever its coefficient; it joins the gradient only when the coefficient is non-zero
     coef = config.get("illegal_action_l2norm_coef", 0.0)
@@ -93,8 +93,7 @@ def ppo_loss(config, logits, value, batch: Transition, gae, targets):
         with torch.no_grad():
             illegal_loss = spectral_norm_nonneg(torch.softmax(logits, dim=-1) * (~mask)) / 2
     total = loss_actor + config["vf_coef"] * value_loss - config["ent_coef"] * entropy
-    if coef:
-        total = total + coef * illegal_loss
+    total = total + float(coef or 0.0) * illegal_loss       # (src/update.py:146-151: also with a zero coefficient — a NaN norm is a NaN total)
     with torch.no_grad():
         approx_kl = ((ratio - 1) - logratio).mean()
         clipfrac = ((ratio - 1.0).abs() > config["clip_eps"]).float().mean()

@@ -337,7 +337,7 @@ int brl_mlp_gemm(int device, int layout, int epilogue, const float *a, int64_t l
         const double bv = layout == 0 ? b[j * ldb + q] : b[q * ldb + j];
         acc += av * bv;
       }
-      if (epilogue == 1) { acc += bias[j]; acc = act == 0 ? (acc > 0 ? acc : 0) : tanh(acc); }
+      if (epilogue == 1) { acc += bias[j]; acc = act == 0 ? (acc <= 0 ? 0 : acc) : tanh(acc); }   /* (a NaN stays NaN) */
       if (epilogue == 2) { const double h = gate[i * ldg + j]; acc = act == 0 ? (h > 0 ? acc : 0) : acc * (1.0 - h * h); }
       const float v = (float)acc;
       c[i * ldc + j] = v;
@@ -446,7 +446,7 @@ int brl_mlp_forward_rows(int device, const brl_mlp_ref *net, const uint8_t *obs,
       for (int64_t j = 0; j < H; j++) {
         double acc = net->b[l][j];
         for (int64_t q = 0; q < k; q++) acc += (double)cur[r * k + q] * (double)net->w[l][j * k + q];
-        dst[r * H + j] = (float)(net->act == 0 ? (acc > 0 ? acc : 0) : tanh(acc));
+        dst[r * H + j] = (float)(net->act == 0 ? (acc <= 0 ? 0 : acc) : tanh(acc));
       }
     cur = dst;
     k = H;
@@ -510,7 +510,8 @@ int brl_adam_shard_apply(int device, float *p, const float *g, float *m, float *
   float sum = 0.0f;
   for (int64_t i = 0; i < (int64_t)G->world * G->nbuckets * G->nsub; i++) sum += partials[i];
   const float norm = sqrtf(sum);
-  const float coef = max_norm > 0.0f ? fminf(max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
+  const float ratio = max_norm / (norm + 1e-6f);   /* torch.clamp(max=1): a NaN norm gives a NaN factor (fminf would return 1) */
+  const float coef = max_norm > 0.0f ? (ratio > 1.0f ? 1.0f : ratio) : 1.0f;
   if (norm_out) *norm_out = norm;
   const float scale = coef * grad_scale, t = *step, rate = lr_dev ? *lr_dev : lr;
   const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t), step_size = rate / bc1, bc2_sqrt = sqrtf(bc2);
@@ -639,7 +640,7 @@ int brl_fair_forward(int device, const brl_fair_net *net, const float *x, int64_
     snprintf(g_err, sizeof(g_err), "bad argument: brl_fair_forward (oracle shim)");
     return BRL_E_ARG;
   }
-#define FAIR_ACT(v) (act == 0 ? ((v) > 0.0 ? (v) : 0.0) : tanh(v))
+#define FAIR_ACT(v) (act == 0 ? ((v) <= 0.0 ? 0.0 : (v)) : tanh(v))   /* (a NaN stays NaN) */
   for (int64_t r = 0; r < rows; r++) {
     double in0[480], cat[680], a[200], bb[200], sc[200], h[39];
     for (int i = 0; i < 480; i++) in0[i] = x[r * 480 + i];

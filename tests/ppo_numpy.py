@@ -89,8 +89,12 @@ def head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tg
     dH = -np.where(mask, p * (np.where(mask, lsm, 0.0) + ent_i[:, None]), 0.0)
     dlogits = dlogits - cfg["ent_coef"] * dH / B
     # the illegal-action term: sigma_1 of the illegal probabilities of the unmasked policy (logged whatever its coefficient)
-    u, s, vt = np.linalg.svd(p_u * ~mask, full_matrices=False)
-    illegal = s[0] / 2
+    if np.isfinite(p_u).all():
+        u, s, vt = np.linalg.svd(p_u * ~mask, full_matrices=False)
+        illegal = s[0] / 2
+    else:        # jnp.linalg.norm of a matrix holding a NaN is NaN (LAPACK's SVD refuses it instead)
+        u, vt = np.full((B, 1), np.nan), np.full((1, p_u.shape[1]), np.nan)
+        illegal = np.nan
     coef = float(cfg.get("illegal_action_l2norm_coef", 0.0) or 0.0)
     total = loss_actor + cfg["vf_coef"] * value_loss - cfg["ent_coef"] * entropy + coef * illegal
     if coef:
@@ -130,7 +134,8 @@ def adam_step(cfg, t, params, m, v, grads, lr=None):
     lr = cfg["lr"] if lr is None else lr
     b1, b2, eps = 0.9, 0.999, 1e-5
     gn = global_norm(grads)
-    scale = min(1.0, cfg["max_grad_norm"] / (gn + 1e-6)) if cfg.get("global_gradient_clipping", True) else 1.0
+    # (np.minimum, as torch.clamp and jnp.minimum: a NaN norm gives a NaN factor; Python's min(1.0, nan) is 1.0)
+    scale = float(np.minimum(1.0, cfg["max_grad_norm"] / (gn + 1e-6))) if cfg.get("global_gradient_clipping", True) else 1.0
     bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
     P, M, V = [], [], []
     for pp, mm, vv, gg in zip(params, m, v, grads):

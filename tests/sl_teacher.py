@@ -168,7 +168,7 @@ def loss64(logits, label, mask, ent_coef):
     lsm = zm - zm.max(1, keepdims=True)
     lsm = lsm - np.log(np.exp(lsm).sum(1, keepdims=True))
     p = np.where(m, np.exp(lsm), 0.0)
-    plogp = np.where(p > 0, p * np.where(m, lsm, 0.0), 0.0)
+    plogp = np.where(p == 0, 0.0, p * np.where(m, lsm, 0.0))      # 0 log 0 = 0; a NaN probability stays NaN (distrax)
     H = -plogp.sum(1)
     tgt = -(onehot * ls2).mean()
     out = np.array([tgt - ent_coef * H.mean(), tgt, H.mean(), (np.argmax(z, 1) == label).mean(), (p2 * ~m).sum(1).mean()])

@@ -130,7 +130,7 @@ def _addresses(snap):
 @pytest.mark.parametrize("model", ["DeepMind", "DeepMind_6"])
 def test_fp32_snapshot_backends_add_every_bias(env, model, backend, monkeypatch):
     """`heads` of an fp32 InferenceSnapshot against forward64 within 2e-4 max(1, max|ref|), at the smallest row count that still takes
-    the backend's path (asserted): torch's _addmm_activation on copies (300 rows) and on views of the module's own parameters,
+    the backend's path (asserted): torch's addmm + relu_ on copies (300 rows) and on views of the module's own parameters,
     brl_mlp_gemm_x3 (4096 rows, BRL_INFERENCE_PLANES=0), brl_linear_x3p with the observation given as bool, as bf16, and cast by the
     library (`env` + own_cast); the two bf16x3 paths also within 1.05 e_lib + 1e-7 scale of the library path's own error; the same
     bound for `hidden` times `head_wt` plus `head_bf`, what a step kernel would form from the stored last layer.  Then the
@@ -245,7 +245,7 @@ def test_16_bit_snapshot_adds_every_bias(env, model, dt, monkeypatch):
 
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 def test_16_bit_snapshot_on_the_library_gemm_adds_every_bias(env, dt, monkeypatch):
-    """BRL_LINEAR16=0: the 16-bit snapshot's hidden layers on torch's _addmm_activation (no `body_nk`): `heads`, `hidden` times
+    """BRL_LINEAR16=0: the 16-bit snapshot's hidden layers on torch's addmm + relu_ (no `body_nk`): `heads`, `hidden` times
     `head_wt` plus `head_bf`, and the plain `refresh` of a 16-bit snapshot, as above"""
     from brl_amd.models import InferenceSnapshot
     monkeypatch.setenv("BRL_LINEAR16", "0")
