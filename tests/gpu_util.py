@@ -74,3 +74,45 @@ def make_env(dds, k, ws=None, lut=None, **kwargs):
                 os.environ.pop(key, None)
             else:
                 os.environ[key] = v
+
+
+def replay_policy_rollout(oracle, ref, traj, sub_actions, seed, reward_scale=7600.0, env_offset=0, detail=None):
+    """Replays the recorded actions of a policy-in-the-loop rollout (sub-step 1: traj.action, sub-steps 2-4:
+    sub_actions) through the oracle's auto_reset(step) and returns the Transition columns the reference's _env_step
+    would have stored (src/roll_out.py:63-103, src/utils.py:69-128): pre-step obs / mask of the acting player (G4),
+    done = OR of the four terminated flags (G2), reward = (r1+r2+r3+r4)[actor] / reward_scale (G1), boards replaced
+    mid-macro-step (G3).  `ref` ends as the post-rollout state (rewards / terminated of the last macro-step).
+    `detail`: a dict that receives, for every sub-step, the pre-step observation and mask of the player to act ("sub_obs"
+    [T, 4, n, 480], "sub_mask" [T, 4, n, 38]) and, appended to detail["events"], the boards that sub-step finished, read off a copy
+    stepped without the re-deal (tests/bidder_net.py: step_with_events, census); detail["t0"] numbers the macro-steps of a later call."""
+    act0, sub = to_np(traj.action), to_np(sub_actions)
+    T, n = act0.shape
+    want = {"obs": np.zeros((T, n, 480), np.uint8), "legal_action_mask": np.zeros((T, n, 38), np.uint8),
+            "done": np.zeros((T, n), np.uint8), "reward": np.zeros((T, n), np.float32)}
+    if detail is not None:
+        from tests.bidder_net import step_with_events
+        detail["sub_obs"], detail["sub_mask"] = np.zeros((T, 4, n, 480), np.uint8), np.zeros((T, 4, n, 38), np.uint8)
+        events, t0 = detail.setdefault("events", []), detail.get("t0", 0)
+    count = 0
+    for t in range(T):
+        want["obs"][t] = ref["observation"]
+        want["legal_action_mask"][t] = ref["legal_action_mask"]
+        actor = ref["current_player"].copy()
+        racc = np.zeros((n, 4), np.float32)
+        term = np.zeros(n, np.int32)
+        for k in range(4):
+            a = act0[t] if k == 0 else sub[t, k - 1]
+            if detail is None:
+                oracle.step(ref, a, autoreset=True, seed=seed, env_offset=env_offset)
+            else:
+                detail["sub_obs"][t, k], detail["sub_mask"][t, k] = ref["observation"], ref["legal_action_mask"]
+                step_with_events(oracle, ref, a, seed, env_offset, t0 + t, k, actor, events)
+            racc += ref["rewards"]
+            term |= ref["terminated"]
+        want["done"][t] = term
+        want["reward"][t] = racc[np.arange(n), actor] / np.float32(reward_scale)
+        count += int(term.sum())
+    ref["rewards"] = racc          # src/utils.py:126-128
+    ref["terminated"] = term
+    want["terminated_count"] = count
+    return want

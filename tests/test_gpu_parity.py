@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests.conftest import synthetic_lut
-from tests.gpu_util import _assert_log_info, assert_state_equal, make_env, random_legal_actions, to_np
+from tests.gpu_util import _assert_log_info, assert_state_equal, make_env, random_legal_actions, replay_policy_rollout, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -433,36 +433,6 @@ def test_policy_step_argmax_and_sample(env, oracle):
     top = lsm.argmax(1)
     emp = counts[np.arange(n), top].sum() / (64 * n)
     assert abs(emp - np.exp(lsm[np.arange(n), top]).mean()) < 0.01
-
-
-def replay_policy_rollout(oracle, ref, traj, sub_actions, seed, reward_scale=7600.0, env_offset=0):
-    """Replays the recorded actions of a policy-in-the-loop rollout (sub-step 1: traj.action, sub-steps 2-4:
-    sub_actions) through the oracle's auto_reset(step) and returns the Transition columns the reference's _env_step
-    would have stored (src/roll_out.py:63-103, src/utils.py:69-128): pre-step obs / mask of the acting player (G4),
-    done = OR of the four terminated flags (G2), reward = (r1+r2+r3+r4)[actor] / reward_scale (G1), boards replaced
-    mid-macro-step (G3).  `ref` ends as the post-rollout state (rewards / terminated of the last macro-step)."""
-    act0, sub = to_np(traj.action), to_np(sub_actions)
-    T, n = act0.shape
-    want = {"obs": np.zeros((T, n, 480), np.uint8), "legal_action_mask": np.zeros((T, n, 38), np.uint8),
-            "done": np.zeros((T, n), np.uint8), "reward": np.zeros((T, n), np.float32)}
-    count = 0
-    for t in range(T):
-        want["obs"][t] = ref["observation"]
-        want["legal_action_mask"][t] = ref["legal_action_mask"]
-        actor = ref["current_player"].copy()
-        racc = np.zeros((n, 4), np.float32)
-        term = np.zeros(n, np.int32)
-        for k in range(4):
-            oracle.step(ref, act0[t] if k == 0 else sub[t, k - 1], autoreset=True, seed=seed, env_offset=env_offset)
-            racc += ref["rewards"]
-            term |= ref["terminated"]
-        want["done"][t] = term
-        want["reward"][t] = racc[np.arange(n), actor] / np.float32(reward_scale)
-        count += int(term.sum())
-    ref["rewards"] = racc          # src/utils.py:126-128
-    ref["terminated"] = term
-    want["terminated_count"] = count
-    return want
 
 
 POLICY_CFG = {"reward_scale": 7600, "game_mode": "competitive", "actor_illegal_action_mask": True,
