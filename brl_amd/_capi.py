@@ -164,6 +164,7 @@ def lib() -> C.CDLL:
     sigs.update(boards_signatures())
     sigs.update(book_argtypes())
     sigs.update(par_argtypes())
+    sigs.update(review_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -230,6 +231,15 @@ def par_argtypes() -> dict:
     return {
         "brl_par": [i32, _vp, _vp, _vp, i64, _vp, _vp],
         "brl_par_imp": [i32, _vp, _vp, i64, i32, _vp, _vp],
+    }
+
+
+def review_argtypes() -> dict:
+    """argtypes of include/brl_review.h (the call review; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_review_expand": [i32, _vp, _vp, i64, i32, _vp, i64, i64, _vp, _vp, _vp],
+        "brl_review_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp, _vp],
     }
 
 

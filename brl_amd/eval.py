@@ -3,6 +3,7 @@
     python -m brl_amd.eval team1_model_path=a.pt team2_model_path=b.pkl [team2_model_type=FAIR] [num_eval_envs=100] [dds_path=...]
                            [deals_path=deals.json|deals.pbn] [save_boards=out.json|out.pbn]
                            [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20] [par=1]
+                           [review=1] [review_depth=12] [save_review=review.json]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -12,6 +13,10 @@ dealing from the table; ``save_boards``: write every board's two auctions, contr
 the first ``book_depth`` calls; entries with fewer than ``book_min_count`` samples are left out) as JSON or, ``.txt``, as a tree.
 ``par=1``: the boards are scored against their double-dummy par (``par.par_stats``): one line per team behind the ``IMP:``
 line, and ``save_boards`` writes the par score, the par contracts and each table's IMP against par too.
+``review=1``: the call review of the match (``review.make_call_review``): at each of the first ``review_depth`` calls of every
+auction every alternative call is played out by the two loaded teams' own greedy policies and scored against the other table's
+recorded result — hindsight on the actual deal, not a double-dummy judgement; one line per team behind the ``IMP:`` line, and
+``save_review`` (which implies ``review=1``) writes the whole review as JSON (``review.CallReview.from_json`` reads it back).
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     team2_activation="relu", team2_model_type="DeepMind", num_eval_envs=100,
     dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
     deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20, par=0,
+    review=0, review_depth=12, save_review=None,
 )
 
 
@@ -33,7 +39,9 @@ def main(argv, log=print):
     cfg = parse(argv, EVAL_DEFAULTS)
     if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
         raise SystemExit("team1_model_path= and team2_model_path= are required")
-    boards_run = cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
+    review = bool(cfg["review"]) or cfg["save_review"] is not None
+    boards_run = (cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
+                  or review)
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -66,6 +74,16 @@ def main(argv, log=print):
         from .par import par_stats, stats_lines
         for line in stats_lines(par_stats(records)):
             log(line)
+    if review:
+        from .review import make_call_review
+        call_review = make_call_review(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                       cfg["team2_model_type"], depth=int(cfg["review_depth"]))
+        rv = call_review(team1, team2, records)
+        for line in rv.stats_lines():
+            log(line)
+        if cfg["save_review"] is not None:
+            rv.to_json(cfg["save_review"])
+            log(f"review: {cfg['save_review']}")
     return float(imp), float(se)
 
 
