@@ -165,6 +165,7 @@ def lib() -> C.CDLL:
     sigs.update(book_argtypes())
     sigs.update(par_argtypes())
     sigs.update(review_argtypes())
+    sigs.update(belief_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -240,6 +241,16 @@ def review_argtypes() -> dict:
     return {
         "brl_review_expand": [i32, _vp, _vp, i64, i32, _vp, i64, i64, _vp, _vp, _vp],
         "brl_review_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp, _vp],
+    }
+
+
+def belief_argtypes() -> dict:
+    """argtypes of include/brl_belief.h (the hand beliefs; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32, u64 = C.c_int64, C.c_int, C.c_uint64
+    return {
+        "brl_belief_deal": [i32, _vp, i64, i64, u64, i64, _vp, _vp, _vp],
+        "brl_belief_logp": [i32, _vp, i64, _vp, i64, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp],
+        "brl_belief_reduce": [i32, _vp, i64, i64, _vp, _vp, _vp, _vp, _vp],
     }
 
 

@@ -243,6 +243,7 @@ __device__ __forceinline__ void auto_reset_clear(Tbl &t) {
 // ---- counter-based RNG: Philox4x32-10 ------------------------------------------------
 constexpr uint32_t STREAM_RESET = 0x42524C52u;   // 'BRLR'
 constexpr uint32_t STREAM_ACTION = 0x42524C41u;  // 'BRLA'
+constexpr uint32_t STREAM_BELIEF = 0x42524C42u;  // 'BRLB': the deals of the hand beliefs (include/brl_belief.h)
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t out[4]) {

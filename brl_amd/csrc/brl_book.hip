@@ -7,6 +7,7 @@
 
 #include "../../include/brl_book.h"
 #include "abi_common.hpp"
+#include "hand_features.hpp"
 
 namespace {
 
@@ -17,24 +18,11 @@ static_assert(sizeof(brl_book_team) == 400 && sizeof(brl_book_entry) == BRL_BOOK
                   offsetof(brl_book_entry, team) == 16 && offsetof(brl_book_team, imp_sum) == 384,
               "entry layout");
 
-// feature word (brl_book.h)
-constexpr int F_LEN = 6, F_BAL = 22, F_TEAM = 23, F_IMP = 24;
-
-__device__ __forceinline__ uint32_t hand_features(uint64_t w) {
-  const uint32_t top = (uint32_t)(w >> 36);   // ranks 9..12: J,Q,K,A, a nibble each
-  const uint32_t hcp = __popc(top & 0xFu) + 2u * __popc(top & 0xF0u) + 3u * __popc(top & 0xF00u) + 4u * __popc(top & 0xF000u);
-  uint32_t f = hcp;
-  uint64_t shape = 0;   // how many suits have each length, four bits per length
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    const uint32_t len = (uint32_t)__popcll((w >> s) & 0x1111111111111ull);
-    f |= len << (F_LEN + 4 * s);
-    shape += 1ull << (4 * len);
-  }
-  const bool bal = shape == ((1ull << 16) | (3ull << 12)) || shape == ((2ull << 16) | (1ull << 12) | (1ull << 8)) ||
-                   shape == ((1ull << 20) | (2ull << 12) | (1ull << 8));   // 4333, 4432, 5332
-  return f | ((uint32_t)bal << F_BAL);
-}
+// feature word (brl_book.h): the hand's part is hand_features.hpp's
+using brl::F_BAL;
+using brl::F_LEN;
+using brl::hand_features;
+constexpr int F_TEAM = 23, F_IMP = 24;
 
 // Four lanes per record: lane q loads bytes 16 q .. 16 q + 15 — the header, hands N,E, hands S,W, calls[0..15] — and owns the
 // seat (dealer + q) & 3, which makes the calls p = q, q + 4, q + 8.

@@ -4,6 +4,7 @@
                            [deals_path=deals.json|deals.pbn] [save_boards=out.json|out.pbn]
                            [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20] [par=1]
                            [review=1] [review_depth=12] [save_review=review.json]
+                           [belief_board=ID belief_table=a belief_call=t] [belief_samples=4096] [save_belief=belief.json]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -17,6 +18,10 @@ line, and ``save_boards`` writes the par score, the par contracts and each table
 auction every alternative call is played out by the two loaded teams' own greedy policies and scored against the other table's
 recorded result — hindsight on the actual deal, not a double-dummy judgement; one line per team behind the ``IMP:`` line, and
 ``save_review`` (which implies ``review=1``) writes the whole review as JSON (``review.CallReview.from_json`` reads it back).
+``belief_board=ID belief_table=a|b belief_call=t``: the hand belief (``belief.make_hand_belief``) of the seat to call at
+decision ``t`` of that board (its ``board_id``; the row of the match where the boards have none) at that table: what the other
+three hands look like to it according to the two loaded teams, from ``belief_samples`` sampled deals — printed behind the other
+lines; ``save_belief`` writes it as JSON (``belief.HandBelief.from_json`` reads it back).
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -28,6 +33,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     dds_path="dds_results/test_000.npy",   # build-side: the reference reads this path unconditionally
     deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20, par=0,
     review=0, review_depth=12, save_review=None,
+    belief_board=None, belief_table="a", belief_call=0, belief_samples=4096, save_belief=None,
 )
 
 
@@ -41,7 +47,7 @@ def main(argv, log=print):
         raise SystemExit("team1_model_path= and team2_model_path= are required")
     review = bool(cfg["review"]) or cfg["save_review"] is not None
     boards_run = (cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
-                  or review)
+                  or review or cfg["belief_board"] is not None)
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -84,6 +90,26 @@ def main(argv, log=print):
         if cfg["save_review"] is not None:
             rv.to_json(cfg["save_review"])
             log(f"review: {cfg['save_review']}")
+    if cfg["belief_board"] is not None:
+        import numpy as np
+
+        from .belief import make_hand_belief, queries_from_records
+        ids = records.board_id
+        if ids is not None and not isinstance(ids, np.ndarray):
+            ids = ids.detach().cpu().numpy()
+        rows = np.nonzero(np.asarray(ids) == int(cfg["belief_board"]))[0] if ids is not None else [int(cfg["belief_board"])]
+        if len(rows) == 0 or not 0 <= int(rows[0]) < len(records):
+            raise SystemExit(f"belief_board={cfg['belief_board']}: no such board in the match")
+        if cfg["belief_table"] not in ("a", "b"):
+            raise SystemExit(f"belief_table={cfg['belief_table']!r}: 'a' or 'b'")
+        hand_belief = make_hand_belief(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                       cfg["team2_model_type"], samples=int(cfg["belief_samples"]))
+        hb = hand_belief(team1, team2, queries_from_records(records, cfg["belief_table"], int(rows[0]), int(cfg["belief_call"])))
+        for line in hb.to_text(0).split("\n"):
+            log(line)
+        if cfg["save_belief"] is not None:
+            hb.to_json(cfg["save_belief"])
+            log(f"belief: {cfg['save_belief']}")
     return float(imp), float(se)
 
 
