@@ -357,7 +357,7 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
 
     from . import _capi
     from ._capi import OBS_SIZE
-    from .evaluation import _Forward
+    from .evaluation import _team_forwards
     from .models import make_forward_pass
     fp1 = make_forward_pass(team1_activation, team1_model_type)
     fp2 = make_forward_pass(team2_activation, team2_model_type)
@@ -370,10 +370,9 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         """logits of one query's K observation rows.  A query's rows always go through the network as one batch of exactly K rows:
         which kernels a forward runs on, and with them the last bits of a logit, depend on the batch's size, so a batch made of
         whatever queries happen to be processed together would make the entries depend on the grouping."""
-        snap = getattr(fwd, "snap", None)
-        as_bf16 = snap is not None and snap.planes_for(K)
-        x = torch.empty((K, OBS_SIZE), dtype=torch.bfloat16 if as_bf16 else torch.float32, device=obs.device)
-        _capi.check(_capi.lib().brl_obs_cast(eval_env._h, obs.data_ptr(), K, _capi.ptr(x), 1 if as_bf16 else 0, _capi.stream()))
+        dtype, fmt = fwd.cast(K)
+        x = torch.empty((K, OBS_SIZE), dtype=dtype, device=obs.device)
+        _capi.check(_capi.lib().brl_obs_cast(eval_env._h, obs.data_ptr(), K, _capi.ptr(x), fmt, _capi.stream()))
         out = fwd(None, x)
         return out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
 
@@ -439,13 +438,12 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         if not queries:
             return HandBelief(np.zeros(0, ENTRY_DTYPE), [], seed=seed)
         with torch.no_grad():
-            fwd1 = _Forward(fp1, team1_params)
-            fwd2 = fwd1 if team2_params is team1_params else _Forward(fp2, team2_params)
+            fwds = _team_forwards(fp1, team1_params, fp2, team2_params)
             parts, order, taken = [], [], []
             for a in range(0, len(queries), per):
                 ids = sorted(range(a, min(len(queries), a + per)), key=lambda i: -len(plans[i]))     # (stable)
                 got = [] if rows is not None else None
-                parts.append(batch((fwd1, fwd2), [queries[i] for i in ids], [plans[i] for i in ids],
+                parts.append(batch(fwds, [queries[i] for i in ids], [plans[i] for i in ids],
                                    [int(query_offset) + i for i in ids], got, counts))
                 order += ids
                 if rows is not None:

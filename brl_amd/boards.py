@@ -436,8 +436,7 @@ class BoardRecords:
 
 
 # ---- a match with its boards ------------------------------------------------------------------------------------------------------
-def make_board_match(eval_env, team1_activation, team1_model_type, team2_activation, team2_model_type, num_eval_envs=None,
-                     sync_every: int = 16):
+def make_board_match(eval_env, team1_activation, team1_model_type, team2_activation, team2_model_type, num_eval_envs=None):
     """``board_match(team1_params, team2_params, deals | rng_key) -> (log, BoardRecords)``: ``make_simple_duplicate_evaluate``'s
     match — the same loop (``evaluation._eval_loop``), the same ``log`` = (mean IMP, standard error, win rate) bit for bit for
     the same key — and the records of both tables of every board.  With a ``Deals`` the given boards are played
@@ -451,7 +450,7 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
 
     from . import _capi
     from .duplicate import Table_info
-    from .evaluation import _eval_loop, _Forward
+    from .evaluation import _eval_loop, _match_stats, _team_forwards
     from .models import make_forward_pass
     fp1 = make_forward_pass(team1_activation, team1_model_type)
     fp2 = make_forward_pass(team2_activation, team2_model_type)
@@ -474,8 +473,7 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
             dda = state._dds_tricks
             table_a_info, table_b_info = Table_info.from_state(state), Table_info.from_state(state)
             cum_return = torch.zeros(n, dtype=torch.float32, device=dev)
-            fwd1 = _Forward(fp1, team1_params)
-            fwd2 = fwd1 if team2_params is team1_params else _Forward(fp2, team2_params)
+            fwd1, fwd2 = _team_forwards(fp1, team1_params, fp2, team2_params)
             prev = state.packed.clone()
             final_a = torch.zeros_like(prev)
             taken = torch.zeros(n, dtype=torch.uint8, device=dev)
@@ -486,10 +484,8 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
                                                _capi.ptr(table_a_info.terminated), _capi.ptr(taken), _capi.ptr(final_a), n,
                                                _capi.stream(di)))
 
-            final, _ = _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None,
-                                  sync_every, after_step=keep_a)
-            fn = float(n)
-            log = (cum_return.mean(), cum_return.std(unbiased=True) / (fn ** 0.5), (cum_return > 0).sum() / fn)
+            final, _ = _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None, after_step=keep_a)
+            log = _match_stats(cum_return, n)
             if not bool(taken.all()):
                 raise RuntimeError("board_match: a board's table A never ended")
             rec_a, rec_b = board_records(final_a), board_records(final.packed)

@@ -7,11 +7,11 @@
   and ``make_evaluate_log`` (:1035-1115), the flat ``eval/...`` dict ppo.py logs every ``num_eval_step`` iterations.
 * ``make_simple_evaluate`` — the single-table deterministic evaluator of src/evaluation.py:11-66.
 
-Every loop iteration is one or two (merged) GEMM forwards in PyTorch-ROCm plus ONE ``brl_eval_step`` launch: team selection,
-masked arg-max, the step log (illegal-action probability mass, step / pass / bid counters), ``duplicate_step`` and the
-return accumulators all happen in that kernel; the end-of-run histograms come from ``brl_eval_reduce`` as exact integer
-counts.  The loop condition ``~state.terminated.all()`` is watched without stalling the GPU (``_DoneWatch``; finished boards
-keep receiving no-op steps, G9, so overshooting changes nothing)."""
+Every iteration of ``_eval_loop`` is one or two forwards (``_Forward.route`` alone decides their input and rows; ``_ActiveRows``
+dispatches on it) plus ONE ``brl_eval_step[_team]`` launch: team selection, masked arg-max, the step log (illegal-action
+probability mass, step / pass / bid counters), ``duplicate_step`` and the return accumulators all happen in that kernel; the
+end-of-run histograms come from ``brl_eval_reduce`` as exact integer counts.  The loop condition ``~state.terminated.all()`` is
+watched without stalling the GPU (``_DoneWatch``; finished boards keep receiving no-op steps, G9: overshooting changes nothing)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -83,14 +83,38 @@ def masked_mode(logits: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 
 
 class _Forward:
-    """logits of one team's network for a batch of observations: the fused inference snapshot when the architecture is
-    covered (DeepMind / ReLU), else the module itself.  Returns a float32 [n, >=38] matrix whose first 38 columns are
-    the logits (row stride may be 39: merged actor + critic heads)."""
+    """logits of one team's network for a batch of observations: the fused inference snapshot when the architecture is covered
+    (DeepMind / ReLU), else the module itself.  Returns a float32 [n, >=38] matrix whose first 38 columns are the logits (row stride
+    may be 39: merged actor + critic heads).  It owns the question "what does this forward take as input, and on which rows":
+    ``route`` for the loops, ``cast`` for a caller that casts the observation itself.  A CONSTANT forward — the same logits whatever
+    the observation (``_PassOnly``, the tests' scripted doubles) — is any object with a ``constant = True`` class attribute and
+    ``__call__(obs_bool, obs_f32)``."""
+    constant = False
 
     def __init__(self, forward_pass, params):
         self.fp, self.params = forward_pass, params
-        self.snap = InferenceSnapshot.make(params, views=os.environ.get("BRL_SNAPSHOT_VIEWS", "1") != "0")
-        self.ref = self._by_reference(params)
+        self.snap = InferenceSnapshot.make(params, views=os.environ.get("BRL_SNAPSHOT_VIEWS", "1") != "0")   # None: the module forwards
+        self.ref = self._by_reference(params)   # None: brl_mlp_forward_rows does not apply
+        self._scratch = None
+
+    def _planes(self, m):   # a forward of m rows runs on brl_linear_x3p: it takes the 0/1 observation as one bf16 plane, or the bool rows
+        return self.snap is not None and bool(self.snap.planes_for(m))
+
+    def cast(self, m):
+        """(dtype, brl_obs_cast[_rows] format code) of the observation ``x`` a forward of m rows takes as ``fwd(None, x)``"""
+        return (torch.bfloat16, 1) if self._planes(m) else (torch.float32, 0)
+
+    @staticmethod
+    def route(fwd, m, shrunk):
+        """how the loops get the logits of ``fwd`` (a ``_Forward`` or a constant forward) for m rows; ``shrunk``: the rows are an
+        index list into a full logits buffer that exists already (``_ActiveRows.forward`` does what the names say)"""
+        if fwd.constant:
+            return "constant"    # fwd(obs_bool, None), nothing else
+        if not shrunk:           # every board: the snapshot takes the bool rows themselves | float32 (the step launch's, else a cast)
+            return "full_bool" if fwd._planes(m) else "full_f32"
+        if m <= _OWN_FORWARD_ROWS and fwd.ref is not None:
+            return "rows_own"    # brl_mlp_forward_rows: the iteration is bound by host launches
+        return "rows_bf16" if fwd._planes(m) else "rows_f32"   # brl_obs_cast_rows (gather + astype), the forward, index_copy_
 
     @staticmethod
     def _by_reference(m):
@@ -120,20 +144,39 @@ class _Forward:
         """logits (+ value) of the boards idx[0..m) written to their rows of ``out`` [n, >= 39]: ONE call into the library"""
         hidden = int(self.ref.hidden)
         need = m * (OBS_SIZE + 2 * hidden)
-        if getattr(self, "_scratch", None) is None or self._scratch.numel() < need:
+        if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.float32, device=out.device)
         check(_capi.lib().brl_mlp_forward_rows(device_index(out), C.byref(self.ref), ptr(obs_bool), ptr(idx), m, ptr(self._scratch),
                                                self._scratch.numel(), out.data_ptr(), out.stride(0), stream()))
 
     def __call__(self, obs_bool, obs_f32):
         if self.snap is not None:
-            # forwards of >= 4096 rows run on brl_linear_x3p (models.InferenceSnapshot.planes_for): it takes the 0/1 observation as bf16
-            # (one plane) — from the bool rows, or already gathered + cast by the caller
-            if obs_bool is not None and self.snap.planes_for(obs_bool.shape[0]):
-                return self.snap.heads(obs_bool)
-            return self.snap.heads(obs_f32)
+            return self.snap.heads(obs_bool if obs_bool is not None and self._planes(obs_bool.shape[0]) else obs_f32)
         logits, _ = self.fp.apply(self.params, obs_f32)
         return logits.contiguous()
+
+
+class _PassOnly:
+    """free-run opponent: probs = one-hot(Pass) (src/evaluation.py:243-247); logits with softmax == that one-hot."""
+    constant = True
+
+    def __init__(self, n, device):
+        self.lg = torch.full((n, NUM_ACTIONS), -1e30, dtype=torch.float32, device=device)
+        self.lg[:, 0] = 0.0
+
+    def __call__(self, obs_bool, obs_f32):
+        return self.lg
+
+
+def _team_forwards(fp1, params1, fp2, params2):
+    """the two teams' forwards: ONE object when the parameter objects are the same"""
+    fwd1 = _Forward(fp1, params1)
+    return fwd1, (fwd1 if params2 is params1 else _Forward(fp2, params2))
+
+
+def _match_stats(cum_return, n):
+    """(mean IMP, standard error, win rate) of the n boards' IMPs of one unsharded match (src/evaluation.py:199-201)"""
+    return cum_return.mean(), cum_return.std(unbiased=True) / (float(n) ** 0.5), (cum_return > 0).sum() / float(n)
 
 
 class EvalStats:
@@ -273,7 +316,7 @@ class _ActiveRows:
     valid board indices — at worst a board is forwarded twice, with identical results)."""
 
     def __init__(self, n):
-        self.n, self.m, self.idx, self.full = n, n, None, None
+        self.n, self.m, self.idx, self.full, self.route = n, n, None, None, None   # (route: the last forward's)
 
     def update(self, polled):
         if polled is None or polled[1] is None:
@@ -293,143 +336,113 @@ class _ActiveRows:
 
     def forward(self, fwd, obs, env, x=None):
         """``x``: the observation as float32 when the launch that produced it wrote that too (brl_eval_step_team.obs_f32)"""
-        if getattr(fwd, "constant", False):   # (the same logits whatever the observation: nothing to compute)
+        shrunk = self.idx is not None and self.full is not None
+        route = self.route = _Forward.route(fwd, self.m if shrunk else obs.shape[0], shrunk)
+        if route == "constant":
             return fwd(obs, None)
-        if self.idx is None or self.full is None:
-            snap = getattr(fwd, "snap", None)
-            if snap is not None and snap.planes_for(obs.shape[0]):      # (takes the bool rows themselves: _Forward.__call__)
-                self.full = fwd(obs, None)
-            else:
-                self.full = fwd(obs, x if x is not None else obs.to(torch.float32))
-            if getattr(fwd, "ref", None) is not None and self.full.stride(0) <= NUM_ACTIONS:
+        if not shrunk:
+            self.full = fwd(obs, None) if route == "full_bool" else fwd(obs, x if x is not None else obs.to(torch.float32))
+            if fwd.ref is not None and self.full.stride(0) <= NUM_ACTIONS:
                 # (the module's own [n, 38] logits: brl_mlp_forward_rows writes 38 + 1 numbers per row later on)
                 wide = torch.empty((self.full.shape[0], NUM_ACTIONS + 2), dtype=torch.float32, device=self.full.device)
                 wide[:, :NUM_ACTIONS] = self.full
                 self.full = wide
-            return self.full
-        if self.m <= _OWN_FORWARD_ROWS and getattr(fwd, "ref", None) is not None:
-            # few boards left: the iteration is bound by host launches — gather + cast, the layers, the heads and the scatter
-            # back in one call (brl_mlp_forward_rows; rows of finished boards keep their last logits: never used)
+        elif route == "rows_own":   # (rows of finished boards keep their last logits: never used)
             fwd.rows(obs, self.idx, self.m, self.full, env)
-            return self.full
-        snap = getattr(fwd, "snap", None)
-        as_bf16 = snap is not None and snap.planes_for(self.m)      # (brl_linear_x3p: the observation as one bf16 plane)
-        x = torch.empty((self.m, OBS_SIZE), dtype=torch.bfloat16 if as_bf16 else torch.float32, device=obs.device)
-        check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(self.idx), self.m, ptr(x), 1 if as_bf16 else 0, stream()))   # gather + astype
-        out = fwd(None, x)
-        self.full[:, :out.shape[1]].index_copy_(0, self.idx, out)   # (rows of finished boards keep their last logits: never used)
+        else:
+            dtype, fmt = fwd.cast(self.m)
+            x = torch.empty((self.m, OBS_SIZE), dtype=dtype, device=obs.device)
+            check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(self.idx), self.m, ptr(x), fmt, stream()))   # gather + astype
+            out = fwd(None, x)
+            self.full[:, :out.shape[1]].index_copy_(0, self.idx, out)
         return self.full
+
+    def takes_f32(self, fwd):   # this team's next forward still takes every board as float32: the step launch before it writes that
+        return self.idx is None and _Forward.route(fwd, self.n, False) == "full_f32"
 
 
 def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward, tables, stats, bid_set, cum_return,
-               rewards_sum, sync_every, record_actions=None, record_logits=None, by_turn=False, record_calls=None, after_step=None):
-    """Runs ``brl_eval_step`` until every board is finished; ``state.packed`` is advanced in place.  (``sync_every`` — how often
-    the loop condition used to be read back — is kept in the signatures and ignored: see ``_DoneWatch``.)  ``after_step(packed,
-    action)``: called behind every step launch with the tables as stepped and the calls made (boards.py keeps table A's final
-    state with it: the launch that ends table A re-deals the slot for table B)."""
-    n, dev = state.num_envs, env.device
-    obs = state.observation
+               rewards_sum, calls=None, logits=None, full=False, by_turn=False, after_step=None):
+    """Runs ``brl_eval_step`` until every board is finished; ``state.packed`` is advanced in place.  One of three loops:
+    * by turn (``by_turn``): call i of every board is made by fwd1 (i even: the player who opened and their partner) or fwd2
+      (i odd) — the macro-step of src/utils.py:133-202 one call at a time, every board in step; ONE forward per call.
+    * alternating (two different networks): the reference evaluates BOTH on every board and selects by team
+      (src/evaluation.py:146-151); here iteration i runs ONE forward (team i & 1's network) and only the boards whose player to
+      act is on that team make their call (brl_eval_step_team).  Calls are deterministic arg-maxes and a board's teams
+      alternate call by call, so every board plays exactly the same auction; it waits at most one iteration at its start and
+      one at the table switch.  Half the GEMM work per board.
+    * lock-step: one network on both sides, or ``full``: the reference's shape — every forward on every board (no live-row
+      compaction), no alternation (the tests' oracle replays).
+    ``calls`` / ``logits``: lists that receive every iteration's calls, [n] int32 (-1: the board waited for its team's
+    iteration) / the lock-step loop's selected logits.  ``after_step(packed, action)``: called behind every step launch with the
+    tables as stepped and the calls made (boards.py keeps table A's final state with it: the launch that ends table A re-deals
+    the slot for table B)."""
+    n, dev, obs = state.num_envs, env.device, state.observation
     term = torch.empty(n, dtype=torch.bool, device=dev)
     action = torch.empty(n, dtype=torch.int32, device=dev)
     pa = tables[0]._ptrs() if tables else None
     pb = tables[1]._ptrs() if tables else None
     ps = stats.ptrs() if stats is not None else None
-    packed = state.packed
-    count = 0
-    # Two different networks: the reference evaluates BOTH on every board and selects by team (src/evaluation.py:146-151);
-    # here the teams take turns — iteration i runs ONE forward (team i & 1's network) and only the boards whose player to
-    # act is on that team make their call (brl_eval_step_team).  Calls are deterministic arg-maxes and a board's teams
-    # alternate call by call, so every board plays exactly the same auction; it waits at most one iteration at its start
-    # and one at the table switch.  Half the GEMM work per board.  (Recording runs — the tests' oracle replays — keep the
-    # reference's lock-step loop.)
-    alternate = (fwd2 is not fwd1) and record_actions is None and record_logits is None
-    compact = record_actions is None and record_logits is None and os.environ.get("BRL_EVAL_COMPACT", "1") != "0"
+    packed, L = state.packed, _capi.lib()
+    head = (env._h, ptr(packed), ptr(packed), n)
+    accumulators = (C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
+                    C.byref(ps) if ps is not None else None, int(bid_set), ptr(cum_return), ptr(rewards_sum), ptr(action))
+
+    def step(l1, l2, nobs, team=None, obs_f32=None):   # (team: only that team's boards call, by l1; obs_f32: written too, if a buffer)
+        if team is None:
+            check(L.brl_eval_step(*head, l1.data_ptr(), l1.stride(0), l2.data_ptr(), l2.stride(0), *accumulators,
+                                  ptr(nobs), None, None, ptr(term), None, stream()))
+        else:
+            check(L.brl_eval_step_team(*head, l1.data_ptr(), l1.stride(0), team, *accumulators,
+                                       ptr(nobs), None, None, ptr(term), None, ptr(obs_f32), stream()))
+
+    mode = "by_turn" if by_turn else "alternate" if (fwd2 is not fwd1 and not full) else "lock_step"
+    compact = not full and os.environ.get("BRL_EVAL_COMPACT", "1") != "0"
     watch = _DoneWatch.take(env, n, compact)
     rows = [_ActiveRows(n), _ActiveRows(n)]   # (one logits buffer per team: their forwards alternate)
-    obs_f32 = None
+    fwds, count, obs_f32 = (fwd1, fwd2), 0, None
     while True:
         polled = watch.poll(count)
         if polled is not None and polled[0] >= n:
             watch.release()   # (an exception above leaves it marked busy: the next loop simply builds its own)
             break
         nobs = torch.empty((n, OBS_SIZE), dtype=torch.bool, device=dev)
-        if by_turn:
-            # the networks take turns by CALL, not by team: call i of every board is made by fwd1 (i even: the player who opened
-            # and their partner) or fwd2 (i odd) — the macro-step of src/utils.py:133-202 one call at a time, every board in step;
-            # ONE forward per call, on the boards still playing
+        if mode == "lock_step":
+            if compact:   # (one network: two networks alternate unless ``full``)
+                rows[0].update(polled)
+                l1 = l2 = rows[0].forward(fwd1, obs, env)
+            else:
+                x = obs.to(torch.float32)
+                l1 = fwd1(obs, x)
+                l2 = fwd2(obs, x) if fwd2 is not fwd1 else l1   # G10: the reference evaluates both networks and selects
+            if logits is not None:
+                team1 = (State(env, packed).current_player < 2)[:, None]
+                logits.append(torch.where(team1, l1[:, :NUM_ACTIONS], l2[:, :NUM_ACTIONS]).clone())
+            step(l1, l2, nobs)
+        else:   # ONE forward, on the boards still playing
             k = count & 1
             rows[k].update(polled)
-            lg = rows[k].forward(fwd2 if k else fwd1, obs, env)
-            check(_capi.lib().brl_eval_step(
-                env._h, ptr(packed), ptr(packed), n, lg.data_ptr(), lg.stride(0), lg.data_ptr(), lg.stride(0),
-                C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
-                C.byref(ps) if ps is not None else None, int(bid_set),
-                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
-            obs = nobs
-            if after_step is not None:
-                after_step(packed, action)
-            if record_actions is not None:
-                record_actions.append(action.clone())
-            watch.post(count, term)
-            count += 1
-            continue
-        if alternate:
-            team = count & 1
-            rows[team].update(polled)
-            lg = rows[team].forward(fwd2 if team else fwd1, obs, env, obs_f32)
-            # the next iteration's forward still takes every board: this launch writes its float32 input as well
-            nxt, nfwd = rows[team ^ 1], (fwd1 if team else fwd2)
-            nsnap = getattr(nfwd, "snap", None)
-            obs_f32 = torch.empty((n, OBS_SIZE), dtype=torch.float32, device=dev) \
-                if (_STEP_CASTS and nxt.idx is None and not getattr(nfwd, "constant", False)
-                    and not (nsnap is not None and nsnap.planes_for(n))) else None
-            check(_capi.lib().brl_eval_step_team(
-                env._h, ptr(packed), ptr(packed), n, lg.data_ptr(), lg.stride(0), team,
-                C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
-                C.byref(ps) if ps is not None else None, int(bid_set),
-                ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, ptr(obs_f32), stream()))
-            if after_step is not None:
-                after_step(packed, action)
-            if record_calls is not None:   # (the calls of THIS loop — -1: the board waited for its team's iteration — for oracle replays)
-                record_calls.append(action.clone())
-            obs = nobs
-            watch.post(count, term)
-            count += 1
-            continue
-        if compact:
-            rows[0].update(polled)
-            rows[1].update(polled)
-            l1 = rows[0].forward(fwd1, obs, env)
-            l2 = rows[1].forward(fwd2, obs, env) if fwd2 is not fwd1 else l1
-        else:
-            x = obs.to(torch.float32)
-            l1 = fwd1(obs, x)
-            l2 = fwd2(obs, x) if fwd2 is not fwd1 else l1   # G10: the reference evaluates both networks and selects
-        if record_logits is not None:
-            team1 = (State(env, packed).current_player < 2)[:, None]
-            record_logits.append(torch.where(team1, l1[:, :NUM_ACTIONS], l2[:, :NUM_ACTIONS]).clone())
-        check(_capi.lib().brl_eval_step(
-            env._h, ptr(packed), ptr(packed), n, l1.data_ptr(), l1.stride(0), l2.data_ptr(), l2.stride(0),
-            C.byref(pa) if pa is not None else None, C.byref(pb) if pb is not None else None,
-            C.byref(ps) if ps is not None else None, int(bid_set),
-            ptr(cum_return), ptr(rewards_sum), ptr(action), ptr(nobs), None, None, ptr(term), None, stream()))
+            lg = rows[k].forward(fwds[k], obs, env, obs_f32)
+            if mode == "alternate":   # (where the other team's forward still takes every board as float32, this launch writes that too)
+                obs_f32 = torch.empty((n, OBS_SIZE), dtype=torch.float32, device=dev) \
+                    if _STEP_CASTS and rows[k ^ 1].takes_f32(fwds[k ^ 1]) else None
+            step(lg, lg, nobs, k if mode == "alternate" else None, obs_f32)
         obs = nobs
         if after_step is not None:
             after_step(packed, action)
-        if record_actions is not None:
-            record_actions.append(action.clone())
+        if calls is not None:
+            calls.append(action.clone())
         watch.post(count, term)
         count += 1
     return State(env, packed, {"observation": obs, "terminated": term}), count
 
 
 def make_simple_duplicate_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, team2_activation,
-                                   team2_model_type, num_eval_envs, sync_every: int = 16, record_actions=None, shard=None,
-                                   record_calls=None):
-    """src/evaluation.py:69-204.  ``record_actions``: optional list that receives each iteration's action tensor
-    (tests replay them through the oracle; the reference's lock-step loop runs).  ``record_calls``: the same for the DEFAULT
-    loop (teams alternate, forwards on the boards still playing): one [n] tensor per iteration, -1 where a board waited.  ``shard`` (see _Shard): the boards are split over the ranks, (mean IMP,
-    standard error, win rate) are those of all ``num_eval_envs`` boards on every rank; the Table_info are this rank's."""
+                                   team2_model_type, num_eval_envs, record_actions=None, shard=None, record_calls=None):
+    """src/evaluation.py:69-204.  ``record_actions``: optional list that receives each iteration's action tensor (tests replay
+    them through the oracle; the reference's lock-step loop runs: ``full``).  ``record_calls``: the same for the DEFAULT loop (teams
+    alternate, forwards on the boards still playing): -1 where a board waited.  ``shard`` (see _Shard): the boards are split over the
+    ranks, (mean IMP, standard error, win rate) are those of all ``num_eval_envs`` boards on every rank; the Table_info are this rank's."""
     team1_forward_pass = make_forward_pass(team1_activation, team1_model_type)
     team2_forward_pass = make_forward_pass(team2_activation, team2_model_type)
 
@@ -440,22 +453,18 @@ def make_simple_duplicate_evaluate(eval_env: BridgeBidding, team1_activation, te
             table_a_info = Table_info.from_state(state)              # :96-103
             table_b_info = Table_info.from_state(state)              # :104-111
             cum_return = torch.zeros(sh.n, dtype=torch.float32, device=eval_env.device)
-            fwd1 = _Forward(team1_forward_pass, team1_params)
-            fwd2 = fwd1 if team2_params is team1_params else _Forward(team2_forward_pass, team2_params)
-            _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None,
-                       sync_every, record_actions, record_calls=record_calls)   # :120-197; cum_return += rewards[:, 0] (G8)
-            n = float(num_eval_envs)
+            fwd1, fwd2 = _team_forwards(team1_forward_pass, team1_params, team2_forward_pass, team2_params)
+            _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None,   # :120-197 (G8)
+                       calls=record_calls if record_actions is None else record_actions, full=record_actions is not None)
             if sh.active:   # sums over every rank's boards (IMPs are integers: exact in float64)
+                n = float(num_eval_envs)
                 x = cum_return.to(torch.float64)
                 t = sh.allsum(torch.stack([x.sum(), (x * x).sum(), (x > 0).sum().to(torch.float64)]))
                 mean = t[0] / n
                 var = ((t[1] - n * mean * mean) / (n - 1.0)).clamp_min(0.0)
                 log_info = (mean.to(torch.float32), (var.sqrt() / (n ** 0.5)).to(torch.float32), (t[2] / n).to(torch.float32))
                 return log_info, table_a_info, table_b_info
-            std_error = cum_return.std(unbiased=True) / (n ** 0.5)   # :199
-            win_rate = (cum_return > 0).sum() / n                    # :200
-            log_info = (cum_return.mean(), std_error, win_rate)
-        return log_info, table_a_info, table_b_info
+            return _match_stats(cum_return, num_eval_envs), table_a_info, table_b_info   # :199-202
 
     return duplicate_evaluate
 
@@ -515,8 +524,8 @@ def eval_log_info(c: torch.Tensor, stats, cum_return: torch.Tensor, dup: bool, s
 
 
 def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, team2_activation, team2_model_type,
-                  team2_params, num_eval_envs, game_mode="competitive", duplicate=False, sync_every: int = 16,
-                  record_actions=None, record_logits=None, shard=None):
+                  team2_params, num_eval_envs, game_mode="competitive", duplicate=False, record_actions=None,
+                  record_logits=None, shard=None):
     """``make_evaluate`` (src/evaluation.py:207-1032).  ``team2_params`` replaces the reference's pickle path.
     Returns ``duplicate_evaluate(actor_params, rng_key) -> (log_info, table_a_info, table_b_info)`` (23-entry
     log_info, :985-1031) or, with ``duplicate=False``, ``evaluate(actor_params, rng_key) -> (state, log_info)``
@@ -528,17 +537,6 @@ def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, t
     opp_forward_pass = make_forward_pass(team2_activation, team2_model_type)
     if game_mode not in ("competitive", "free-run"):
         raise ValueError(game_mode)
-
-    class _PassOnly:
-        """free-run opponent: probs = one-hot(Pass) (src/evaluation.py:243-247); logits with softmax == that one-hot."""
-        constant = True
-
-        def __init__(self, n, device):
-            self.lg = torch.full((n, NUM_ACTIONS), -1e30, dtype=torch.float32, device=device)
-            self.lg[:, 0] = 0.0
-
-        def __call__(self, obs_bool, obs_f32):
-            return self.lg
 
     def run(actor_params, rng_key, dup):
         sh = _Shard(num_eval_envs, shard)   # (shard: the statistics below are those of all boards, on every rank; the
@@ -553,7 +551,8 @@ def make_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, t
             fwd2 = _PassOnly(n, dev) if game_mode == "free-run" else _Forward(opp_forward_pass, team2_params)
             # the single-table evaluator marks a bid as made (.set(1), :349-358), the duplicate one counts it (:704-713)
             state, _ = _eval_loop(eval_env, state, fwd1, fwd2, tables, stats, 0 if dup else 1, cum_return, rewards_sum,
-                                  sync_every, record_actions, record_logits)
+                                  calls=record_actions, logits=record_logits,
+                                  full=record_actions is not None or record_logits is not None)
             if not dup:  # make_terminated_log on the final state (:463-487): one "table" built from it
                 f = State(eval_env, state.packed)
                 tables = (Table_info(f.terminated, rewards_sum, f._last_bid, f._last_bidder, f._call_x, f._call_xx),)
@@ -608,8 +607,7 @@ def make_evaluate_log(log_info):
 
 
 def make_simple_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_type, team2_activation,
-                         team2_model_type, team2_params, num_eval_envs, sync_every: int = 8, shard=None,
-                         record_actions=None, record_calls=None):
+                         team2_model_type, team2_params, num_eval_envs, shard=None, record_actions=None, record_calls=None):
     """src/evaluation.py:11-66: actor (greedy) vs a fixed opponent (greedy) on single tables, no
     auto-reset; returns the mean total reward of the acting player.  ``team2_params`` replaces the
     reference's pickle path (model files are torch modules here).  ``record_actions``: optional list that receives,
@@ -630,7 +628,7 @@ def make_simple_evaluate(eval_env: BridgeBidding, team1_activation, team1_model_
             opener = state.current_player.to(torch.int64)
             rsum = torch.zeros((sh.n, 4), dtype=torch.float32, device=eval_env.device)
             _eval_loop(eval_env, state, _Forward(actor_forward_pass, actor_params), _Forward(opp_forward_pass, team2_params),
-                       None, None, 0, None, rsum, sync_every, record_actions=record_calls, by_turn=True)
+                       None, None, 0, None, rsum, calls=record_calls, full=record_calls is not None, by_turn=True)
             R = rsum.gather(1, opener[:, None])[:, 0]
         if sh.active:   # (scores are integers: the float64 sum over the ranks is exact)
             return (sh.allsum(R.to(torch.float64).sum().reshape(1))[0] / float(num_eval_envs)).to(torch.float32)

@@ -150,7 +150,7 @@ def make_league_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
                     fwds[k] = _Forward(forward_pass, params_list[k])
             state = sh.init(eval_env, rng_key)
             tables = (Table_info.from_state(state), Table_info.from_state(state))
-            _eval_loop(eval_env, state, fwds[i], fwds[j], tables, None, 0, cum[p], None, 16)
+            _eval_loop(eval_env, state, fwds[i], fwds[j], tables, None, 0, cum[p], None)
 
     def play_batched(refs, pairs, rng_key, sh, cum):
         n = sh.n

@@ -223,7 +223,7 @@ def make_call_review(eval_env, team1_activation, team1_model_type, team2_activat
 
     from .boards import board_records
     from .bridge_bidding import State
-    from .evaluation import _eval_loop, _Forward
+    from .evaluation import _eval_loop, _team_forwards
     from .models import make_forward_pass
     fp1 = make_forward_pass(team1_activation, team1_model_type)
     fp2 = make_forward_pass(team2_activation, team2_model_type)
@@ -247,8 +247,7 @@ def make_call_review(eval_env, team1_activation, team1_model_type, team2_activat
             dda = dda.to(device=dev, dtype=torch.uint8).reshape(-1, 20).contiguous()
             if not (recs["a"].shape[0] == recs["b"].shape[0] == dda.shape[0]):
                 raise ValueError("call_review: table A, table B and dda hold different numbers of boards")
-            fwd1 = _Forward(fp1, team1_params)
-            fwd2 = fwd1 if team2_params is team1_params else _Forward(fp2, team2_params)
+            fwd1, fwd2 = _team_forwards(fp1, team1_params, fp2, team2_params)
             skipped, parts = {}, []
             for table in tables:
                 rec, other = recs[table], recs["ab"["ba".index(table)]]
@@ -259,7 +258,7 @@ def make_call_review(eval_env, team1_activation, team1_model_type, team2_activat
                 for d0 in range(0, total, per):
                     d1 = min(total, d0 + per)
                     decisions, branch = expand(rec, dda, depth, first, d0, d1)
-                    _eval_loop(eval_env, State(eval_env, branch), fwd1, fwd2, None, None, 0, None, None, 16)
+                    _eval_loop(eval_env, State(eval_env, branch), fwd1, fwd2, None, None, 0, None, None)
                     v, s = reduce(branch, decisions, other)
                     dec.append(decisions)
                     val.append(v)

@@ -1,5 +1,6 @@
 """configs[2] (8192-board duplicate evaluation, two DeepMind MLPs, fp32) iteration by iteration: rows forwarded (the batch-size
-ladder of brl_amd/evaluation.py::_ActiveRows), GPU time between the iterations' ends (events) and host time per iteration.
+ladder of brl_amd/evaluation.py::_ActiveRows) and their route (_Forward.route), GPU time between the iterations' ends (events) and
+host time per iteration.
 usage (GPU box): python scripts/eval_ladder_probe.py [out.txt]"""
 import os
 import sys
@@ -36,7 +37,7 @@ def main():
         r = orig(self, fwd, obs, env_, x)
         e = torch.cuda.Event(enable_timing=True)
         e.record()
-        log.append((self.m if self.idx is not None else self.n, e, time.perf_counter()))
+        log.append((self.m if self.idx is not None else self.n, e, time.perf_counter(), self.route))
         return r
 
     ev._ActiveRows.forward = probe
@@ -48,12 +49,12 @@ def main():
     total = time.perf_counter() - h0
     ev._ActiveRows.forward = orig
     out = [f"duplicate evaluation, {NUM_ENVS} boards: {plain * 1e3:.2f} ms unprobed, {total * 1e3:.2f} ms probed, {len(log)} iterations",
-           "iter  rows  gpu_us(since previous forward's end)  host_us"]
+           "iter  rows  gpu_us(since previous forward's end)  host_us  route"]
     prev_e, prev_h = start, h0
     by_m = {}
-    for i, (m, e, h) in enumerate(log):
+    for i, (m, e, h, route) in enumerate(log):
         g = prev_e.elapsed_time(e) * 1e3
-        out.append(f"{i:4d} {m:5d} {g:9.1f} {(h - prev_h) * 1e6:9.1f}")
+        out.append(f"{i:4d} {m:5d} {g:9.1f} {(h - prev_h) * 1e6:9.1f}  {route}")
         by_m.setdefault(m, []).append(g)
         prev_e, prev_h = e, h
     out.append("rows: iterations, total gpu ms, mean us")

@@ -34,8 +34,9 @@ def main():
             fwd.rows(obs, idx, m, full, env)
 
         def lib():
-            x = torch.empty((m, 480), dtype=torch.float32, device=dev)
-            check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(idx), m, ptr(x), 0, _stream()))
+            dtype, fmt = fwd.cast(m)   # (what _ActiveRows.forward does on the rows_bf16 / rows_f32 routes)
+            x = torch.empty((m, 480), dtype=dtype, device=dev)
+            check(_capi.lib().brl_obs_cast_rows(env._h, ptr(obs), ptr(idx), m, ptr(x), fmt, _stream()))
             full.index_copy_(0, idx, fwd(None, x))
 
         res = []

@@ -129,8 +129,8 @@ def measure(nets):
     out["expand"] = {"decisions": nd, "us_per_launch": us, "runs_us": runs, "bytes_written": written, "GB_per_s": written / us / 1e3,
                      "copy_us": cus, "copy_runs_us": cruns, "launch_over_copy": us / cus}
     decisions, branch = review.expand(rec, dda, DEPTH, first, 0, nd)
-    evaluation._eval_loop(env, brl_amd.bridge_bidding.State(env, branch), evaluation._Forward(fp, nets[0]), evaluation._Forward(fp, nets[1]),
-                          None, None, 0, None, None, 16)
+    evaluation._eval_loop(env, brl_amd.bridge_bidding.State(env, branch), *evaluation._team_forwards(fp, nets[0], fp, nets[1]),
+                          None, None, 0, None, None)
     us, runs = launches(lambda: review.reduce(branch, decisions, records.table_b))
     written, read = nd * review.ACTIONS + nd * 8, nd * review.ACTIONS * 40 + nd * 16
     cus, cruns = copy_us(written)

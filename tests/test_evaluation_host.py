@@ -1,5 +1,5 @@
 """Host-side logic of the evaluators' loop (brl_amd/evaluation.py) that needs no GPU: the ladder of batch sizes the forwards on
-the boards still playing step down through (`_ActiveRows.update`), and the composition of ``log_info`` from the counters of ``brl_eval_reduce`` (`eval_log_info`)."""
+the boards still playing step down through (`_ActiveRows.update`), the route of every forward (`_Forward.route`), and the composition of ``log_info`` from the counters of ``brl_eval_reduce`` (`eval_log_info`)."""
 import numpy as np
 import pytest
 import torch
@@ -42,6 +42,61 @@ def test_batch_size_never_grows_and_ignores_missing_lists():
     assert rows.m == 1536
     rows.update((100, idx))            # an older, larger count arriving late must not grow the batch again
     assert rows.m == 1536
+
+
+class _SnapStub:
+    """a snapshot as far as the route is concerned: brl_linear_x3p from 4096 rows on (models.InferenceSnapshot.planes_for)"""
+
+    def planes_for(self, rows):
+        return rows >= 4096
+
+
+class _ConstantStub:
+    """the whole contract of a constant forward (evaluation._Forward's docstring)"""
+    constant = True
+
+    def __call__(self, obs_bool, obs_f32):
+        raise AssertionError("the route needs no forward")
+
+
+def _stub_forwards():
+    """(constant, snapshot + brl_mlp_ref: "DeepMind" ReLU, brl_mlp_ref only: "DeepMind" tanh, neither: "FAIR")"""
+    from brl_amd.evaluation import _Forward
+    out = [_ConstantStub()]
+    for snap, ref in ((_SnapStub(), object()), (None, object()), (None, None)):
+        f = object.__new__(_Forward)       # (no network behind it: route and cast read these two attributes only)
+        f.snap, f.ref = snap, ref
+        out.append(f)
+    return out
+
+
+def test_route_of_every_forward_at_every_threshold(monkeypatch):
+    """_Forward.route — what a forward takes as input and on which rows — on both sides of _OWN_FORWARD_ROWS = 1024 and of the
+    4096-row planes threshold, for every kind of forward; and when the alternating loop's step launch writes float32 too"""
+    from brl_amd import evaluation
+    from brl_amd.evaluation import _Forward
+    monkeypatch.setattr(evaluation, "_OWN_FORWARD_ROWS", 1024)
+    constant, relu, tanh, fair = _stub_forwards()
+    full, shrunk = (300, 4095, 4096, 8192), (256, 1024, 1280, 3072, 4096, 6144)
+    want = {constant: (["constant"] * 4, ["constant"] * 6),
+            relu: (["full_f32", "full_f32", "full_bool", "full_bool"],
+                   ["rows_own", "rows_own", "rows_f32", "rows_f32", "rows_bf16", "rows_bf16"]),
+            tanh: (["full_f32"] * 4, ["rows_own", "rows_own", "rows_f32", "rows_f32", "rows_f32", "rows_f32"]),
+            fair: (["full_f32"] * 4, ["rows_f32"] * 6)}
+    for fwd, (w_full, w_shrunk) in want.items():
+        assert [_Forward.route(fwd, n, False) for n in full] == w_full
+        assert [_Forward.route(fwd, m, True) for m in shrunk] == w_shrunk
+    for fwd in (relu, tanh, fair):
+        assert [fwd.cast(m) for m in (4095, 4096)] == [(torch.float32, 0), (torch.bfloat16 if fwd is relu else torch.float32, int(fwd is relu))]
+    monkeypatch.setattr(evaluation, "_OWN_FORWARD_ROWS", 0)        # BRL_EVAL_OWN_ROWS=0: never the one-call forward
+    assert [_Forward.route(relu, m, True) for m in (256, 4096)] == ["rows_f32", "rows_bf16"]
+    # the step launch writes the next forward's float32 input exactly while that forward takes every board as float32
+    for n in full:
+        for fwd in (constant, relu, tanh, fair):
+            rows = _ActiveRows(n)
+            assert rows.takes_f32(fwd) == (fwd is not constant and not (fwd is relu and n >= 4096)), n
+            rows.update((n - 1, torch.arange(n)))                   # an index list: from now on the forward gathers its own rows
+            assert rows.idx is not None and not rows.takes_f32(fwd)
 
 
 def test_done_watch_tags_identify_loop_and_iteration():

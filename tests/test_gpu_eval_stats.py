@@ -148,8 +148,8 @@ def _play(dds, m, rows, dup, alternate, bid_set, prefill=0):
     stats.bid_count.fill_(prefill)
     rec = []
     with torch.no_grad():
-        state, count = _eval_loop(env, st, f1, f2, tables, stats, bid_set, cum, rsum, 16, record_actions=None if alternate else rec,
-                                  record_calls=rec if alternate else None, after_step=script.after_step)
+        state, count = _eval_loop(env, st, f1, f2, tables, stats, bid_set, cum, rsum, calls=rec, full=not alternate,
+                                  after_step=script.after_step)
         if not dup:
             f = State(env, state.packed)
             tables = (brl_amd.Table_info(f.terminated, rsum, f._last_bid, f._last_bidder, f._call_x, f._call_xx),)
