@@ -166,6 +166,7 @@ def lib() -> C.CDLL:
     sigs.update(par_argtypes())
     sigs.update(review_argtypes())
     sigs.update(belief_argtypes())
+    sigs.update(belief_smc_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -251,6 +252,16 @@ def belief_argtypes() -> dict:
         "brl_belief_deal": [i32, _vp, i64, i64, u64, i64, _vp, _vp, _vp],
         "brl_belief_logp": [i32, _vp, i64, _vp, i64, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp],
         "brl_belief_reduce": [i32, _vp, i64, i64, _vp, _vp, _vp, _vp, _vp],
+    }
+
+
+def belief_smc_argtypes() -> dict:
+    """argtypes of include/brl_belief_smc.h (the beliefs' resample-move stages; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32, u64 = C.c_int64, C.c_int, C.c_uint64
+    return {
+        "brl_belief_resample": [i32, _vp, i64, _vp, i64, i64, u64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "brl_belief_propose": [i32, _vp, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp],
+        "brl_belief_accept": [i32, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     }
 
 

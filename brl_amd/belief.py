@@ -9,6 +9,12 @@ hidden call is the network's masked arg-max, the policy the evaluators play).  N
 * ``BeliefQuery(seat, hand, dealer, vul, calls, seating=...)``; ``queries_from_records(records, table, board, call_index)``.
 * ``make_hand_belief(eval_env, ...)`` -> ``hand_belief(team1_params, team2_params, queries) -> HandBelief``.
 * ``HandBelief`` — numpy arrays on the host, with ``of``, ``to_text``, ``to_json`` / ``from_json``, ``same_as``.
+
+Opt-in (``make_hand_belief(..., resample_every=R, moves=M)``, include/brl_belief_smc.h): a resample-move particle
+filter for auctions that starve plain importance sampling.  After every R-th weighed call of a query its deals are resampled in
+proportion to their weights (``brl_belief_resample``) and each copy is moved M times: one card exchanged between two hidden hands
+(``brl_belief_propose``), the prefix so far replayed on the proposed deal through the same forwards, and the exchange taken by the
+likelihood ratio (``brl_belief_accept``).  ``resample_every=0`` is the plain path, call for call.
 """
 from __future__ import annotations
 
@@ -21,6 +27,10 @@ from .boards import CALL_NAMES, MAX_CALLS, RANKS, SEATS, SUITS, VULS, bit_card, 
 ACTIONS = 38                      # BRL_BELIEF_ACTIONS
 STREAM = 0x42524C42               # BRL_BELIEF_STREAM
 ALL_ACTIONS = (1 << ACTIONS) - 1
+RESAMPLE_STREAM = 0x42524C53      # BRL_BELIEF_RESAMPLE_STREAM
+MOVE_STREAM = 0x42524C4D          # BRL_BELIEF_MOVE_STREAM
+MAX_MOVES = 256                   # BRL_BELIEF_SMC_MAX_MOVES
+SMC_FIELDS = ("resamples", "proposals", "accepted", "distinct")
 
 QUERY_DTYPE = np.dtype([("hand", "<u8"), ("seat", "u1"), ("dealer", "u1"), ("vul_ns", "u1"), ("vul_ew", "u1"), ("seating", "u1"),
                         ("zero", "u1", 3)])
@@ -188,6 +198,20 @@ def queries_from_records(records, table, board, call_index):
     return out
 
 
+def resample_stages(query, resample_every: int, index=0) -> list:
+    """the call indices after which ``query`` resamples (include/brl_belief_smc.h, schedule): every ``resample_every``-th of the
+    calls a hidden seat made; none with ``resample_every`` = 0, a prefix without a hidden call or no prefix at all"""
+    R = int(resample_every)
+    if R < 0:
+        raise ValueError("resample_every >= 0")
+    out, weighed = [], 0
+    for t, (seat, _, _) in enumerate(query.plan(index)):
+        weighed += seat != query.seat
+        if R and seat != query.seat and weighed % R == 0:
+            out.append(t)
+    return out
+
+
 def query_array(queries) -> np.ndarray:
     q = np.zeros(len(queries), QUERY_DTYPE)
     for i, x in enumerate(queries):
@@ -208,13 +232,19 @@ class HandBelief:
       card_prob [Q,3,52], hcp_hist [Q,3,38], hcp_mean [Q,3], length_hist [Q,3,4,14], length_mean [Q,3,4], balanced [Q,3]:
       the weighted sums over wsum (NaN throughout where the query's weights are not finite);
       greedy_card_prob, greedy_hcp_hist, greedy_hcp_mean, greedy_length_hist, greedy_length_mean, greedy_balanced: the counts over
-      the consistent samples divided by ``consistent`` (NaN where it is 0)."""
+      the consistent samples divided by ``consistent`` (NaN where it is 0).
+      With resampling (``smc``: a dict of the four arrays; all four ``None`` without it): resamples [Q] the resamplings a query
+      went through, proposals, accepted [Q] its particles' moves, distinct [Q] the different deals among its final particles.
+      ``ess`` then counts only the weight since the last resampling — ``distinct`` is the number that shows degeneracy — and the
+      consistent samples are the greedy-consistent ones among the soft particles, not a rejection sample."""
 
-    def __init__(self, entries, queries, samples=None, seed=0):
+    def __init__(self, entries, queries, samples=None, seed=0, smc=None):
         e = np.ascontiguousarray(entries).view(ENTRY_DTYPE).reshape(-1)
         self.entries, self.queries = e, [q if isinstance(q, dict) else q.label() for q in queries]
         assert len(self.queries) == len(e)
         self.seed = int(seed)
+        for name in SMC_FIELDS:
+            setattr(self, name, None if smc is None else np.asarray(smc[name], np.int64).reshape(len(e)).copy())
         own = np.array([SEATS.index(q["seat"]) for q in self.queries], np.int64).reshape(-1)
         self.seats = ((own[:, None] + np.arange(1, 4)[None, :]) & 3).astype(np.uint8)
         self.n, self.consistent = e["n"].astype(np.int64), e["consistent"].astype(np.int64)
@@ -243,6 +273,8 @@ class HandBelief:
         """query q as plain Python: the query's label, n, ess, consistent, and per hidden seat name the soft and the greedy
         {hcp_mean, hcp_range (10 % and 90 % points), length_mean {suit: x}, balanced, cards {name: probability}}"""
         out = dict(self.queries[q], n=int(self.n[q]), ess=float(self.ess[q]), consistent=int(self.consistent[q]), hidden={})
+        if self.resamples is not None:
+            out.update({name: int(getattr(self, name)[q]) for name in SMC_FIELDS})
         own = hand_word(self.queries[q]["hand"])
         for h in range(3):
             views = {}
@@ -260,12 +292,17 @@ class HandBelief:
 
     def to_text(self, q: int, honours: int = 3) -> str:
         """query q for reading: per hidden seat the HCP mean and 10-90 % range, the suit lengths, the share of balanced hands and
-        the most and least likely honours, the soft belief with the greedy one beside it after ``|``; the first line holds the
-        effective sample size and the consistent count, so that a starved belief shows"""
+        the most and least likely honours, the soft belief with the greedy one beside it after ``|``; the second line holds the
+        effective sample size and the consistent count, so that a starved belief shows — with resampling the effective size
+        since the last resampling, the resamplings, the distinct deals, the moves taken, and the greedy column's name: the
+        greedy-consistent among the soft particles"""
         d = self.of(q)
         lines = [f"belief {q}: {d['seat']} holds {d['hand']}; dealer {d['dealer']}, vul {d['vul']}; "
                  f"auction {' '.join(d['calls']) if d['calls'] else '(none)'}",
                  f"  {d['n']} samples, effective {d['ess']:.1f}, consistent with the greedy policy {d['consistent']}"]
+        if self.resamples is not None:
+            lines[1] = (f"  {d['n']} particles, {d['resamples']} resamplings, effective {d['ess']:.1f} since the last, distinct deals "
+                        f"{d['distinct']}, moves taken {d['accepted']} of {d['proposals']}, greedy among soft particles {d['consistent']}")
         for seat, v in d["hidden"].items():
             s, g = v["soft"], v["greedy"]
             lines.append(f"  {seat}: HCP {s['hcp_mean']:.2f} ({s['hcp_range'][0]}-{s['hcp_range'][1]}) | {g['hcp_mean']:.2f} "
@@ -286,6 +323,8 @@ class HandBelief:
                "summary": [{"n": int(self.n[i]), "ess": float(self.ess[i]), "consistent": int(self.consistent[i]),
                             "hcp_mean": self.hcp_mean[i].tolist(), "greedy_hcp_mean": self.greedy_hcp_mean[i].tolist()}
                            for i in range(len(e))]}
+        if self.resamples is not None:
+            doc["smc"] = {name: getattr(self, name).tolist() for name in SMC_FIELDS}
         with open(path, "w") as f:
             json.dump(doc, f)
 
@@ -297,7 +336,7 @@ class HandBelief:
         for i, row in enumerate(doc["entries"]):
             for name in ENTRY_DTYPE.names:
                 e[name][i] = np.asarray(row[name], ENTRY_DTYPE.fields[name][0].base)
-        return cls(e, doc["queries"], seed=doc["seed"])
+        return cls(e, doc["queries"], seed=doc["seed"], smc=doc.get("smc"))
 
     def same_as(self, other) -> bool:
         """the same bytes (NaN blocks included) for the same queries"""
@@ -340,8 +379,43 @@ def reduce(queries_dev, K, hands, logw, greedy):
     return entries
 
 
+def resample(qlist, stream_of, K, seed, stage, tables, hands, logl, logw, greedy):
+    """(tables, hands, logl, logw, greedy, ancestor int32 [Q * K]) of one ``brl_belief_resample`` launch, out of place: only the
+    rows of the queries ``qlist`` (int32 [L]) are written, the others are uninitialised; stream_of int64 [Q]"""
+    import torch
+
+    from . import _capi
+    Q, di = stream_of.shape[0], _capi.device_index(tables)
+    out = [torch.empty_like(x) for x in (tables, hands, logl, logw, greedy)]
+    ancestor = torch.empty(Q * int(K), dtype=torch.int32, device=tables.device)
+    _capi.check(_capi.lib().brl_belief_resample(di, _capi.ptr(qlist), qlist.shape[0], _capi.ptr(stream_of), Q, int(K),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage), _capi.ptr(tables), _capi.ptr(hands),
+                                                _capi.ptr(logl), _capi.ptr(logw), _capi.ptr(greedy), *[_capi.ptr(x) for x in out],
+                                                _capi.ptr(ancestor), _capi.stream(di)))
+    return (*out, ancestor)
+
+
+def propose(queries_dev, qlist, stream_of, K, seed, stage, move, hands, tables_new, hands_new):
+    """one ``brl_belief_propose`` launch: the proposals of the queries ``qlist`` into the leading L * K rows of tables_new / hands_new"""
+    from . import _capi
+    di = _capi.device_index(hands)
+    _capi.check(_capi.lib().brl_belief_propose(di, _capi.ptr(queries_dev), _capi.ptr(qlist), qlist.shape[0], _capi.ptr(stream_of),
+                                               stream_of.shape[0], int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage), int(move),
+                                               _capi.ptr(hands), _capi.ptr(tables_new), _capi.ptr(hands_new), _capi.stream(di)))
+
+
+def accept(qlist, stream_of, K, seed, stage, move, tables_new, hands_new, logl_new, greedy_new, tables, hands, logl, greedy, counters):
+    """one ``brl_belief_accept`` launch: tables / hands / logl / greedy updated in place, counters int64 [Q, 2] added to"""
+    from . import _capi
+    di = _capi.device_index(hands)
+    _capi.check(_capi.lib().brl_belief_accept(di, _capi.ptr(qlist), qlist.shape[0], _capi.ptr(stream_of), stream_of.shape[0], int(K),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage), int(move), _capi.ptr(tables_new),
+                                              _capi.ptr(hands_new), _capi.ptr(logl_new), _capi.ptr(greedy_new), _capi.ptr(tables),
+                                              _capi.ptr(hands), _capi.ptr(logl), _capi.ptr(greedy), _capi.ptr(counters), _capi.stream(di)))
+
+
 def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activation, team2_model_type, samples: int = 4096,
-                     seed: int = 0, max_rows: int = MAX_ROWS):
+                     seed: int = 0, max_rows: int = MAX_ROWS, resample_every: int = 0, moves: int = 2):
     """``hand_belief(team1_params, team2_params, queries, query_offset=0, rows=None, counts=None) -> HandBelief``.
 
     ``queries``: ``BeliefQuery`` s; query i draws its ``samples`` deals from stream ``query_offset + i`` of ``seed``, so a list
@@ -351,7 +425,13 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
     rows still in their auction are always the leading ones.  A query's rows are forwarded as a batch of their own (``samples``
     rows), so the result depends neither on the batches nor on the order nor on the other queries of the call.
     ``rows``: a list that receives per query {"hands" uint64 [K,4], "logw" float32 [K], "greedy" uint8 [K]} as the device left
-    them; ``counts``: a dict whose "forwarded" grows by the rows that went through a network.  Runs on one rank."""
+    them; ``counts``: a dict whose "forwarded" grows by the rows that went through a network.  Runs on one rank.
+    ``resample_every`` = R > 0 (include/brl_belief_smc.h): a query resamples after every R-th call a hidden seat made, and every
+    resampling is followed by ``moves`` Metropolis moves per particle, each of which replays the prefix so far on the proposed
+    deals — the listed queries' rows, again K at a time through the networks, so the batches, the order and the other queries
+    still do not matter.  The schedule follows from the prefixes: the loop still reads nothing back.  ``rows`` then also holds
+    "logl" float32 [K]; the ``HandBelief`` carries ``resamples``, ``proposals``, ``accepted`` and ``distinct``.  R = 0 (the
+    default) is the plain path: the same launches, the same bytes."""
     import torch
     import torch.distributed as dist
 
@@ -364,6 +444,9 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
     K = int(samples)
     if K < 1 or int(max_rows) < K:
         raise ValueError("samples >= 1 and max_rows >= samples")
+    R, M = int(resample_every), int(moves)
+    if R < 0 or not 0 <= M <= MAX_MOVES:
+        raise ValueError(f"resample_every >= 0 and 0 <= moves <= {MAX_MOVES}")
     per = int(max_rows) // K
 
     def forward(fwd, obs):
@@ -377,7 +460,8 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         return out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
 
     def batch(fwds, qs, plans, q_index, rows, counts):
-        """the entries of the queries ``qs`` (already ordered by falling prefix length), stream indices ``q_index``"""
+        """the entries of the queries ``qs`` (already ordered by falling prefix length), stream indices ``q_index``, and with
+        resampling their {resamples, proposals, accepted, distinct} (None without)"""
         dev, L = eval_env.device, _capi.lib()
         Q = len(qs)
         n = Q * K
@@ -395,6 +479,12 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         logw = torch.zeros(n, dtype=torch.float32, device=dev)
         greedy = torch.ones(n, dtype=torch.uint8, device=dev)
         depth = max(T) if T else 0
+        smc = R > 0
+        if smc:
+            stages = [resample_stages(q, R) for q in qs]
+            logl = torch.zeros(n, dtype=torch.float32, device=dev)
+            unused = torch.ones(n, dtype=torch.uint8, device=dev)          # (the flags of the second logp, the one that adds to logl)
+            counters = torch.zeros((Q, 2), dtype=torch.int64, device=dev)
         if depth:
             legal_np, act_np = np.zeros((depth, Q), np.int64), np.zeros((depth, Q), np.int32)
             hidden = [[] for _ in range(depth)]            # per call index: (query, team) of the calls a hidden seat made
@@ -410,25 +500,92 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
             query_of64 = query_of.to(torch.int64)
             row_index = torch.arange(n, dtype=torch.int64, device=dev)
             di = _capi.device_index(tables)
+
+            def step(tb, m, action):
+                _capi.check(L.brl_step(eval_env._h, _capi.ptr(tb), _capi.ptr(tb), m, _capi.ptr(action), 0, None, None, None, None, None,
+                                       _capi.stream(di)))
+
+            def weigh(tb, m, callers, rows_of, legal, action, sums):
+                """one call of the weight on the leading m rows of ``tb``: ``callers`` [(position of the query's K rows, team)],
+                every (logw, greedy) pair of ``sums`` receives the call's term"""
+                obs = torch.empty((m, OBS_SIZE), dtype=torch.bool, device=dev)
+                _capi.check(L.brl_observe(eval_env._h, _capi.ptr(tb), m, None, _capi.ptr(obs), None, _capi.stream()))
+                for i, team in callers:
+                    lg = forward(fwds[team], obs[i * K:(i + 1) * K])
+                    for lw, g in sums:
+                        logp(lg, row_index[i * K:(i + 1) * K], rows_of, legal, action, lw, g)
+                if counts is not None:
+                    counts["forwarded"] = counts.get("forwarded", 0) + len(callers) * K
+
+            if smc and any(stages):
+                # everything a stage needs, on the device before the loop: the queries that resample after call t (ascending: all
+                # of them are still in their auction), and the query of every row of their compact proposal arrays
+                at = {}
+                for i, st in enumerate(stages):
+                    for t in st:
+                        at.setdefault(t, []).append(i)
+                stage_dev = {t: (torch.tensor(ids, dtype=torch.int32, device=dev),
+                                 torch.tensor(ids, dtype=torch.int32, device=dev).repeat_interleave(K)) for t, ids in at.items()}
+                widest = max(len(ids) for ids in at.values()) * K
+                stream_of = torch.tensor(q_index, dtype=torch.int64, device=dev)
+                tables_new = torch.empty((widest, 16), dtype=torch.int64, device=dev)
+                hands_new = torch.empty((widest, 4), dtype=torch.int64, device=dev)
+                logl_new = torch.empty(widest, dtype=torch.float32, device=dev)
+                greedy_new = torch.empty(widest, dtype=torch.uint8, device=dev)
+                team_at = [dict(h) for h in hidden]          # per call index: {query: team} of the hidden callers
+            else:
+                at = {}
+
+            def resample_move(t):
+                ids = at[t]
+                qlist, rows_of = stage_dev[t]
+                m = len(ids) * K
+                out = resample(qlist, stream_of, K, seed, t, tables, hands, logl, logw, greedy)
+                a = 0
+                while a < len(ids):                          # a run of neighbouring queries is one copy per array
+                    b = a + 1
+                    while b < len(ids) and ids[b] == ids[b - 1] + 1:
+                        b += 1
+                    lo, hi = ids[a] * K, (ids[b - 1] + 1) * K
+                    for dst, src in zip((tables, hands, logl, logw, greedy), out):
+                        dst[lo:hi].copy_(src[lo:hi])
+                    a = b
+                rows_of64 = rows_of.to(torch.int64)
+                for move in range(M):
+                    propose(qdev, qlist, stream_of, K, seed, t, move, hands, tables_new, hands_new)
+                    logl_new[:m].zero_()
+                    greedy_new[:m].fill_(1)
+                    for u in range(t + 1):                   # the replay: calls 0..t on the proposed deals, as the live ones went
+                        callers = [(p, team_at[u][i]) for p, i in enumerate(ids) if i in team_at[u]]
+                        if callers:
+                            weigh(tables_new, m, callers, rows_of, legal_dev[u], act_dev[u], [(logl_new, greedy_new)])
+                        step(tables_new, m, act_dev[u].index_select(0, rows_of64))
+                    accept(qlist, stream_of, K, seed, t, move, tables_new, hands_new, logl_new, greedy_new, tables, hands, logl, greedy,
+                           counters)
+
             for t in range(depth):
                 nt = int(live[t]) * K                      # the rows still in their auction: the leading ones
                 if hidden[t]:
-                    obs = torch.empty((nt, OBS_SIZE), dtype=torch.bool, device=dev)
-                    _capi.check(L.brl_observe(eval_env._h, _capi.ptr(tables), nt, None, _capi.ptr(obs), None, _capi.stream()))
-                    for i, team in hidden[t]:
-                        lg = forward(fwds[team], obs[i * K:(i + 1) * K])
-                        logp(lg, row_index[i * K:(i + 1) * K], query_of, legal_dev[t], act_dev[t], logw, greedy)
-                    if counts is not None:
-                        counts["forwarded"] = counts.get("forwarded", 0) + len(hidden[t]) * K
-                action = act_dev[t].index_select(0, query_of64[:nt])
-                _capi.check(L.brl_step(eval_env._h, _capi.ptr(tables), _capi.ptr(tables), nt, _capi.ptr(action), 0, None, None, None,
-                                       None, None, _capi.stream(di)))
+                    weigh(tables, nt, hidden[t], query_of, legal_dev[t], act_dev[t],
+                          [(logw, greedy), (logl, unused)] if smc else [(logw, greedy)])
+                step(tables, nt, act_dev[t].index_select(0, query_of64[:nt]))
+                if t in at:
+                    resample_move(t)
         entries = reduce(qdev, K, hands, logw, greedy)
+        if rows is not None or smc:
+            h = hands.cpu().numpy().view(np.uint64).reshape(Q, K, 4)
         if rows is not None:
-            h, lw, g = hands.cpu().numpy().view(np.uint64).reshape(Q, K, 4), logw.cpu().numpy().reshape(Q, K), greedy.cpu().numpy().reshape(Q, K)
+            lw, g = logw.cpu().numpy().reshape(Q, K), greedy.cpu().numpy().reshape(Q, K)
+            ll = logl.cpu().numpy().reshape(Q, K) if smc else None
             for i in range(Q):
                 rows.append({"hands": h[i].copy(), "logw": lw[i].copy(), "greedy": g[i].copy()})
-        return entries
+                if smc:
+                    rows[-1]["logl"] = ll[i].copy()
+        if not smc:
+            return entries, None
+        c = counters.cpu().numpy()
+        return entries, {"resamples": np.array([len(st) for st in stages], np.int64), "proposals": c[:, 0], "accepted": c[:, 1],
+                         "distinct": np.array([len(np.unique(h[i], axis=0)) for i in range(Q)], np.int64)}
 
     def hand_belief(team1_params, team2_params, queries, query_offset: int = 0, rows=None, counts=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -436,7 +593,7 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         queries = list(queries)
         plans = [q.plan(i) for i, q in enumerate(queries)]          # refuses an illegal prefix before anything is sampled
         if not queries:
-            return HandBelief(np.zeros(0, ENTRY_DTYPE), [], seed=seed)
+            return HandBelief(np.zeros(0, ENTRY_DTYPE), [], seed=seed, smc={name: [] for name in SMC_FIELDS} if R > 0 else None)
         with torch.no_grad():
             fwds = _team_forwards(fp1, team1_params, fp2, team2_params)
             parts, order, taken = [], [], []
@@ -448,14 +605,19 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
                 order += ids
                 if rows is not None:
                     taken += got
-            host = torch.cat(parts).cpu().numpy().view(ENTRY_DTYPE).reshape(-1)
+            host = torch.cat([p[0] for p in parts]).cpu().numpy().view(ENTRY_DTYPE).reshape(-1)
         entries = np.zeros(len(queries), ENTRY_DTYPE)
         entries[np.asarray(order)] = host
+        smc = None
+        if R > 0:
+            smc = {name: np.zeros(len(queries), np.int64) for name in SMC_FIELDS}
+            for name in SMC_FIELDS:
+                smc[name][np.asarray(order)] = np.concatenate([p[1][name] for p in parts])
         if rows is not None:
             back = [None] * len(queries)
             for i, r in zip(order, taken):
                 back[i] = r
             rows.extend(back)
-        return HandBelief(entries, queries, seed=seed)
+        return HandBelief(entries, queries, seed=seed, smc=smc)
 
     return hand_belief

@@ -244,6 +244,8 @@ __device__ __forceinline__ void auto_reset_clear(Tbl &t) {
 constexpr uint32_t STREAM_RESET = 0x42524C52u;   // 'BRLR'
 constexpr uint32_t STREAM_ACTION = 0x42524C41u;  // 'BRLA'
 constexpr uint32_t STREAM_BELIEF = 0x42524C42u;  // 'BRLB': the deals of the hand beliefs (include/brl_belief.h)
+constexpr uint32_t STREAM_BELIEF_RESAMPLE = 0x42524C53u;  // 'BRLS': a resampling's offset (include/brl_belief_smc.h)
+constexpr uint32_t STREAM_BELIEF_MOVE = 0x42524C4Du;      // 'BRLM': a move's proposal and acceptance (include/brl_belief_smc.h)
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t out[4]) {

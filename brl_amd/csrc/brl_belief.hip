@@ -10,6 +10,7 @@
 
 #include "../../include/brl_belief.h"
 #include "abi_common.hpp"
+#include "belief_table.hpp"
 #include "bridge_device.hpp"
 #include "hand_features.hpp"
 #include "policy_common.hpp"
@@ -30,8 +31,7 @@ constexpr uint64_t DECK = (1ull << 52) - 1;
 constexpr int HIDDEN = 39;
 
 // ---- the deals ------------------------------------------------------------------------------------------------------------------
-constexpr int DEAL_LANES = 64;
-constexpr int IMG_STRIDE = 144;   // a lane's 128-byte table image, padded: 16-byte aligned and not a multiple of the 256-byte bank cycle
+constexpr int DEAL_LANES = BELIEF_LANES, IMG_STRIDE = BELIEF_IMG_STRIDE;
 
 __global__ __launch_bounds__(DEAL_LANES) void k_belief_deal(const uint4 *queries, int64_t Q, int64_t K, uint32_t k0, uint32_t k1, int64_t q0,
                                                             uint4 *tables, uint4 *hands) {
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(DEAL_LANES) void k_belief_deal(const uint4 *queries
   const int64_t qi = row / K, k = row - qi * K;
   const uint4 qv = queries[qi];
   const uint64_t own = ((uint64_t)qv.x | ((uint64_t)qv.y << 32)) & DECK;
-  const uint32_t seat = qv.z & 3u, dealer = (qv.z >> 8) & 3u, vns = (qv.z >> 16) & 1u, vew = (qv.z >> 24) & 1u, seating = qv.w & 0xFFu;
+  const BeliefSeat qs = belief_seat(qv);
 
   uint8_t *c = s_cards + lane;
   uint64_t rest = ~own & DECK;
@@ -76,41 +76,10 @@ __global__ __launch_bounds__(DEAL_LANES) void k_belief_deal(const uint4 *queries
     for (int i = 0; i < 13; i++) h[s] |= 1ull << (c[(s * 13 + i) * DEAL_LANES] & 63u);
   }
 
-  // the empty table of the deal, with the words and helpers k_init_explicit uses
-  uint8_t *img = s_img + lane * IMG_STRIDE;
-  uint64_t *img64 = reinterpret_cast<uint64_t *>(img);
-#pragma unroll
-  for (int w = 0; w < W_HAND; w++) img64[w] = 0ull;
-  img64[W_HAND + seat] = own << 4;
-  img64[W_HAND + ((seat + 1u) & 3u)] = h[0] << 4;
-  img64[W_HAND + ((seat + 2u) & 3u)] = h[1] << 4;
-  img64[W_HAND + ((seat + 3u) & 3u)] = h[2] << 4;
-  Tbl t;
-  t.sc = dealer | (vns << SC_VULNS) | (vew << SC_VULEW) | (seating << SC_SHUF);
-  t.sch = 0;
-  t.fd = 0;
-  t.lut = 0xFFFFFFFFu;
-  t.bctr = 0;
-  t.r01 = 0;
-  t.r23 = 0;
-  pack_tricks(t, 0u, 0u, 0u, 0u);
-  store_scalars(t, img);
+  // the empty table of the deal (belief_table.hpp), then the wave's 64 tables and hand rows as whole 16-byte pieces
+  belief_empty_table(s_img + lane * IMG_STRIDE, qs, own, h);
   wave_lds_fence();
-
-  // the wave's 64 x 128 contiguous table bytes and 64 x 32 hand bytes, 16 per lane and store
-#pragma unroll
-  for (int it = 0; it < DEAL_LANES * (TABLE_BYTES / 16) / DEAL_LANES; it++) {
-    const int p = it * DEAL_LANES + lane, smp = p >> 3, piece = p & 7;
-    const uint4 v = *reinterpret_cast<const uint4 *>(s_img + smp * IMG_STRIDE + piece * 16);
-    if (row0 + smp < total) tables[row0 * (TABLE_BYTES / 16) + p] = v;
-  }
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const int p = it * DEAL_LANES + lane, smp = p >> 1, half = p & 1;
-    const uint64_t *src = reinterpret_cast<const uint64_t *>(s_img + smp * IMG_STRIDE) + W_HAND + 2 * half;
-    const uint64_t a = src[0] >> 4, b = src[1] >> 4;
-    if (row0 + smp < total) hands[row0 * 2 + p] = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-  }
+  belief_store_images(s_img, lane, row0, total - row0, tables, hands);
 }
 
 // ---- one call of the weight -----------------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
                            [save_book=book.json|book.txt] [book_depth=4] [book_min_count=20] [par=1]
                            [review=1] [review_depth=12] [save_review=review.json]
                            [belief_board=ID belief_table=a belief_call=t] [belief_samples=4096] [save_belief=belief.json]
+                           [belief_resample=N] [belief_moves=2]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -21,7 +22,9 @@ recorded result — hindsight on the actual deal, not a double-dummy judgement; 
 ``belief_board=ID belief_table=a|b belief_call=t``: the hand belief (``belief.make_hand_belief``) of the seat to call at
 decision ``t`` of that board (its ``board_id``; the row of the match where the boards have none) at that table: what the other
 three hands look like to it according to the two loaded teams, from ``belief_samples`` sampled deals — printed behind the other
-lines; ``save_belief`` writes it as JSON (``belief.HandBelief.from_json`` reads it back).
+lines; ``save_belief`` writes it as JSON (``belief.HandBelief.from_json`` reads it back).  ``belief_resample=N`` (with
+``belief_moves=M`` Metropolis moves per particle, default 2) resamples the deals after every N-th call a hidden seat made
+(``make_hand_belief``'s ``resample_every``): for prefixes that leave plain weighting with a handful of deals.
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     deals_path=None, save_boards=None, save_book=None, book_depth=4, book_min_count=20, par=0,
     review=0, review_depth=12, save_review=None,
     belief_board=None, belief_table="a", belief_call=0, belief_samples=4096, save_belief=None,
+    belief_resample=0, belief_moves=2,
 )
 
 
@@ -103,7 +107,8 @@ def main(argv, log=print):
         if cfg["belief_table"] not in ("a", "b"):
             raise SystemExit(f"belief_table={cfg['belief_table']!r}: 'a' or 'b'")
         hand_belief = make_hand_belief(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
-                                       cfg["team2_model_type"], samples=int(cfg["belief_samples"]))
+                                       cfg["team2_model_type"], samples=int(cfg["belief_samples"]),
+                                       resample_every=int(cfg["belief_resample"]), moves=int(cfg["belief_moves"]))
         hb = hand_belief(team1, team2, queries_from_records(records, cfg["belief_table"], int(rows[0]), int(cfg["belief_call"])))
         for line in hb.to_text(0).split("\n"):
             log(line)
