@@ -120,13 +120,11 @@ class ActorCritic(nn.Module):
 
 
 class InferenceSnapshot:
-    """Inference-only copy of a "DeepMind" ReLU ActorCritic (no autograd): weights transposed (and cast to `dtype`
-    when given) ONCE, bias in the GEMM (``torch.addmm``) + ``relu_`` (which keeps a NaN; the library's fused ReLU epilogue does not), the actor and
-    critic heads as one 39-row GEMM.  With a 16-bit `dtype` and a library handle (`env`) the hidden layers run on the
-    library's own kernel instead (``brl_linear_act``) and ``head_parts`` lets the last layer's launch compute the heads'
-    share (``brl_linear_act_heads``).  Build one per rollout / evaluation call — it does not follow later weight
-    updates (``refresh`` re-reads them in place).  ``make`` returns None for architectures it does not cover (callers fall
-    back to ``module(x)``)."""
+    """Inference-only copy of a "DeepMind" ReLU ActorCritic (no autograd): the weights in the layout of each backend that can run
+    its hidden layers, the actor and critic heads as one 39-row GEMM.  ``__init__`` builds the weight stores a configuration allows,
+    ``route_of`` decides per CALL which backend runs (it depends on the row count and on the tensor handed in), one ``_run_*`` per
+    backend runs it.  Build one per rollout / evaluation call — it does not follow later weight updates (``refresh`` re-reads them
+    in place).  ``make`` returns None for architectures it does not cover (callers fall back to ``module(x)``)."""
 
     def __init__(self, module: "ActorCritic", dtype=None, env=None, own_cast=True, views=False, gemm=None):
         # env: a BridgeBidding whose library runs the 16-bit hidden layers (brl_linear_act) and — own_cast — converts the 0/1
@@ -136,11 +134,10 @@ class InferenceSnapshot:
         self.own_cast = bool(own_cast)
         self.dtype = dtype or torch.float32
         dt = self.dtype
-        # gemm (config["inference_gemm"], else BRL_INFERENCE_GEMM, else "bf16x3"): "bf16x3" = fp32 forwards of >= 4096 rows run their hidden
-        # layers on brl_mlp_gemm_x3 — the fp32 product as six bf16 MFMA products of three EXACT bf16 pieces per operand, fp32 accumulators
-        # by magnitude class: 0.07-0.44 x the exact fp32 kernel's error against float64 and 1.4 x its rate on such batches
-        # (csrc/mlp_gemm_x3.hpp) — on nn.Linear's own [out, in] weights; "library" = torch's fp32 GEMM for every batch.
-        # Either way an fp32 forward (src/models.py:23-33); the two are not bit-identical to each other.
+        self._body_stale = False
+        # gemm (config["inference_gemm"], else BRL_INFERENCE_GEMM, else "bf16x3"): "bf16x3" = the bf16x3 products for large fp32 forwards
+        # (brl_mlp_gemm_x3 on nn.Linear's own [out, in] weights: csrc/mlp_gemm_x3.hpp); "library" = torch's fp32 GEMM for
+        # every batch.  Either way an fp32 forward (src/models.py:23-33); the two are not bit-identical to each other.
         self.gemm_x3 = (gemm or os.environ.get("BRL_INFERENCE_GEMM", "") or "bf16x3") == "bf16x3" and dt == torch.float32 \
             and all(lin.weight.shape[1] % 32 == 0 and lin.weight.shape[0] % 4 == 0 for lin in module.body)   # (whole 32-deep K chunks)
         # nn.Linear's own [out, in] layout: the module's parameters themselves under `views`, else copies `refresh` re-reads (their
@@ -150,10 +147,9 @@ class InferenceSnapshot:
         if self.gemm_x3:
             self.lin = [(lin.weight.detach(), lin.bias.detach()) if views else (lin.weight.detach().clone(), lin.bias.detach().clone())
                         for lin in module.body]
-            # ... and, where the shapes allow (out % 128, in % 32), on brl_linear_x3p (csrc/mlp_linear_x3p.hpp): the SAME products on
-            # operands already split into bf16 planes — the weights here, once per refresh (they are constant over a rollout's 128
-            # forwards), an activation by the launch that produces it — so that the K loop has no vector work.
-            # BRL_INFERENCE_PLANES=0: brl_mlp_gemm_x3 (the split in registers) for every layer.
+            # ... and, where the shapes allow (out % 128, in % 32), for brl_linear_x3p (csrc/mlp_linear_x3p.hpp): the SAME
+            # products on operands already split into bf16 planes — the weights here, once per refresh, an activation by the launch
+            # that produces it.  BRL_INFERENCE_PLANES=0: no planes (the split in registers for every layer).
             if os.environ.get("BRL_INFERENCE_PLANES", "1") != "0" and all(
                     w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.shape[0] % 128 == 0 and w.shape[1] % 32 == 0
                     and w.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 for w, b in self.lin):
@@ -221,14 +217,9 @@ class InferenceSnapshot:
             di = _capi.device_index(w)
             _capi.check(L.brl_split_planes(di, w.data_ptr(), w.numel(), wp.data_ptr(), w.numel(), _capi.stream(di)))
 
-    def planes_for(self, n):
-        """True where a forward of `n` rows runs on brl_linear_x3p: its input may then come as bf16 (the 0/1 observation is exact in it)"""
-        return self.wp is not None and n >= 4096
-
-    def _body_planes(self, x):
-        """the hidden layers on brl_linear_x3p: x bf16 [n, in] — the 0/1 observation, exact as given: ONE plane (an fp32 input stays on
-        brl_mlp_gemm_x3: splitting it first costs what the first layer then saves); every layer writes the planes of its output, the last
-        one fp32 (what the heads' product reads)"""
+    def _run_planes(self, x):
+        """brl_linear_x3p: x bf16 [n, in] — the 0/1 observation, exact as given: ONE plane (an fp32 input stays on brl_mlp_gemm_x3: splitting
+        it first costs what the first layer then saves); every layer writes the planes of its output, the last one fp32 for the heads"""
         from . import _capi
         di = _capi.device_index(x)
         L, st = _capi.lib(), _capi.stream(di)
@@ -266,7 +257,7 @@ class InferenceSnapshot:
             copy_all(b16, [lin.bias.detach() for lin in module.body] + [module.actor.bias.detach(), module.critic.bias.detach()])
             copy_all([b for _, b in self.body_nk] + [self.head_bf], [b for _, b in self.body] + [self.head_b])
             self.head_w.copy_(self.head_wt.t())
-        self._body_stale = True   # self.body's weights ([in, out]) no longer match: rebuilt on demand (_body)
+        self._body_stale = True   # self.body's weights ([in, out]) no longer match: rebuilt on demand (_run_library)
 
     @staticmethod
     def covers(module):
@@ -280,55 +271,84 @@ class InferenceSnapshot:
         return InferenceSnapshot(module, dtype, env, own_cast, views, gemm)
 
     _FMT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+    X3_ROWS = 4096   # rows from which an fp32 forward runs on the bf16x3 kernels (below, torch's GEMM is the faster one)
+
+    @staticmethod
+    def route_of(has16, has_planes, has_x3, snap_dtype, n, xdt, dev_ok, al16):
+        """WHICH backend runs the hidden layers of one call: the first rule that holds.  Of the snapshot: has16 =
+        ``body_nk``, has_planes = ``wp``, has_x3 = ``gemm_x3``, its dtype; of the input x: rows, dtype, dev_ok = on the GPU, 2-D and
+        contiguous, al16 = 16-byte aligned.  Everything else that asks about the backend is derived from this table."""
+        S = InferenceSnapshot
+        if has16 and dev_ok and n > 0:
+            return "linear16"     # brl_linear_act, any row count
+        if has_planes and n >= S.X3_ROWS and dev_ok and al16 and xdt == torch.bfloat16:
+            return "planes"       # brl_linear_x3p on the 0/1 observation as ONE exact bf16 plane
+        if xdt != snap_dtype:
+            raise RuntimeError(f"InferenceSnapshot: input in {xdt} where the layers run in {snap_dtype} (bf16 input is taken by the "
+                               f"planes path only: >= {S.X3_ROWS} contiguous rows)")
+        return "x3" if has_x3 and dev_ok and al16 and n >= S.X3_ROWS else "library"   # brl_mlp_gemm_x3 | torch's addmm + relu_
+
+    def route(self, x):
+        """``route_of`` for the input tensor x (what ``_input`` returned, or a caller's own cast)"""
+        two = x.dim() == 2
+        return self.route_of(self.body_nk is not None, self.wp is not None, self.gemm_x3, self.dtype, x.shape[0] if two else 0, x.dtype,
+                             two and x.is_cuda and x.is_contiguous(), x.data_ptr() % 16 == 0)
+
+    def planes_for(self, n):
+        """rule 2 can apply at `n` rows (brl_linear_x3p): the input may then come as bf16"""
+        return self.wp is not None and n >= self.X3_ROWS
+
+    def input_dtype(self, n, odt=torch.bool, odim=2):
+        """the dtype ``_input`` hands the layers for an observation (a step kernel that casts for them writes this): bf16 where the planes
+        can take the rows and it is exact in bf16 (0/1 bytes, or bf16 as given: brl_obs_cast_rows, format 1), else the snapshot's"""
+        exact = odim == 2 and odt in (torch.bool, torch.uint8, torch.bfloat16)
+        return torch.bfloat16 if exact and self.planes_for(n) else self.dtype
 
     def _input(self, obs):
+        dt = self.input_dtype(obs.shape[0] if obs.dim() == 2 else 0, obs.dtype, obs.dim())
         if self.env is not None and self.own_cast and obs.dtype in (torch.bool, torch.uint8) and obs.is_cuda and obs.is_contiguous() \
                 and self.dtype in self._FMT:
             from . import _capi
-            dt = torch.bfloat16 if (self.dtype == torch.float32 and obs.dim() == 2 and self.planes_for(obs.shape[0])) else self.dtype
             x = torch.empty(obs.shape, dtype=dt, device=obs.device)
             _capi.check(_capi.lib().brl_obs_cast(self.env._h, obs.data_ptr(), obs.numel() // 480, x.data_ptr(), self._FMT[dt], _capi.stream()))
             return x
-        if self.dtype == torch.float32 and obs.dim() == 2 and self.planes_for(obs.shape[0]):
-            if obs.dtype in (torch.bool, torch.uint8):
-                return obs.to(torch.bfloat16)      # 0 / 1: exact — one plane for brl_linear_x3p
-            if obs.dtype == torch.bfloat16:
-                return obs                         # (already cast by the caller: brl_obs_cast_rows with format 1)
-        return obs.to(self.dtype)
+        return obs.to(dt)      # (a bf16 observation on its way to the planes: returned as it is)
 
     def _body(self, x):
-        """the hidden layers: x [n, 480] in ``self.dtype`` -> [n, hidden]"""
-        if self.body_nk is not None and x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] > 0:
-            from . import _capi
-            L, fmt, st = _capi.lib(), self._FMT[self.dtype], _capi.stream()
-            for w, b in self.body_nk:
-                y = torch.empty((x.shape[0], w.shape[0]), dtype=self.dtype, device=x.device)
-                _capi.check(L.brl_linear_act(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(),
-                                           y.data_ptr(), y.stride(0), x.shape[0], w.shape[0], w.shape[1], 1, fmt, st))
-                x = y
-            return x
-        if x.dim() == 2 and self.planes_for(x.shape[0]) and x.is_cuda and x.is_contiguous() and x.data_ptr() % 16 == 0 \
-                and x.dtype == torch.bfloat16 and self.dtype == torch.float32:
-            return self._body_planes(x)
-        if x.dtype != self.dtype:
-            raise RuntimeError(f"InferenceSnapshot: input in {x.dtype} where the layers run in {self.dtype} (bf16 input is taken by the "
-                               "planes path only: >= 4096 contiguous rows)")
-        if self.gemm_x3 and x.is_cuda and x.dim() == 2 and x.shape[0] >= 4096 and x.is_contiguous() and x.data_ptr() % 16 == 0:
-            from . import _capi
-            di = _capi.device_index(x)
-            L, st = _capi.lib(), _capi.stream(di)
-            for w, b in self.lin:      # nn.Linear's own layout: y = relu(x W^T + b), W [out, in]
-                y = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
-                _capi.check(L.brl_mlp_gemm_x3(di, 0, 1, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
-                                              x.shape[0], w.shape[0], w.shape[1], 0, b.data_ptr(), None, 0, None, None, 0, st))
-                x = y
-            return x
-        if getattr(self, "_body_stale", False):   # (only after a 16-bit refresh, and only if this path is taken at all)
+        """the hidden layers: x [n, 480] in ``self.dtype`` (bf16 for the planes) -> [n, hidden]"""
+        return getattr(self, "_run_" + self.route(x))(x)
+
+    def _run_linear16(self, x, layers=None):
+        """brl_linear_act (csrc/mlp_infer.hpp) for every layer of `layers` (default: all of ``body_nk``)"""
+        from . import _capi
+        L, fmt, st = _capi.lib(), self._FMT[self.dtype], _capi.stream()
+        for w, b in self.body_nk if layers is None else layers:
+            y = torch.empty((x.shape[0], w.shape[0]), dtype=self.dtype, device=x.device)
+            _capi.check(L.brl_linear_act(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(),
+                                         y.data_ptr(), y.stride(0), x.shape[0], w.shape[0], w.shape[1], 1, fmt, st))
+            x = y
+        return x
+
+    def _run_x3(self, x):
+        """brl_mlp_gemm_x3 on nn.Linear's own layout: y = relu(x W^T + b), W [out, in]"""
+        from . import _capi
+        di = _capi.device_index(x)
+        L, st = _capi.lib(), _capi.stream(di)
+        for w, b in self.lin:
+            y = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+            _capi.check(L.brl_mlp_gemm_x3(di, 0, 1, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
+                                          x.shape[0], w.shape[0], w.shape[1], 0, b.data_ptr(), None, 0, None, None, 0, st))
+            x = y
+        return x
+
+    def _run_library(self, x):
+        """torch's GEMM on the transposed [in, out] copies, the bias in it (``addmm``), then ``relu_`` — not torch._addmm_activation:
+        the library's fused ReLU epilogue is max(x, 0), which returns 0 for a NaN pre-activation — a NaN weight would vanish behind
+        the layer; relu_ keeps it ("Non-finite values")"""
+        if self._body_stale:   # (a 16-bit refresh wrote body_nk only: the copies follow when this path is taken at all)
             for (w, _), (wn, _) in zip(self.body, self.body_nk):
                 w.copy_(wn.t())
             self._body_stale = False
-        # (addmm + relu_, not torch._addmm_activation: the library's fused ReLU epilogue is max(x, 0), which returns 0 for a NaN
-        #  pre-activation — a NaN weight would vanish behind the layer; relu_ keeps it.  DESIGN.md, "Non-finite values")
         for w, b in self.body:
             x = torch.addmm(b, x, w).relu_()
         return x
@@ -338,21 +358,17 @@ class InferenceSnapshot:
     def head_parts(self, obs, x=None):
         """obs -> the heads as PARTIAL products f32 [hidden / 128, n, 40] (brl_linear_act_heads: the last hidden layer multiplies
         each of its 128-column tiles with the head weights while it holds it, and is itself never written to memory);
-        ``brl_policy_step_ex`` adds the parts and the bias (brl_macro_ext.head_part).  None when the library's own layer kernel
-        does not apply (fp32, no handle, other widths): callers use ``hidden`` / ``heads``."""
+        ``brl_policy_step_ex`` adds the parts and the bias (brl_macro_ext.head_part).  None off the "linear16" route and under
+        BRL_HEAD_PARTS=0: callers use ``hidden`` / ``heads``."""
         if self.body_nk is None or os.environ.get("BRL_HEAD_PARTS", "1") == "0":
-            return None
+            return None        # (whatever the input: nothing is cast for the question)
         if x is None:
             x = self._input(obs)
-        if not (x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] > 0):
+        if self.route(x) != "linear16":
             return None
+        x = self._run_linear16(x, self.body_nk[:-1])
         from . import _capi
         L, fmt, st, n = _capi.lib(), self._FMT[self.dtype], _capi.stream(), x.shape[0]
-        for w, b in self.body_nk[:-1]:
-            y = torch.empty((n, w.shape[0]), dtype=self.dtype, device=x.device)
-            _capi.check(L.brl_linear_act(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(),
-                                         y.data_ptr(), y.stride(0), n, w.shape[0], w.shape[1], 1, fmt, st))
-            x = y
         w, b = self.body_nk[-1]
         parts = torch.empty((w.shape[0] // 128, n, self.HEAD_PART_LD), dtype=torch.float32, device=x.device)
         _capi.check(L.brl_linear_act_heads(self.env._h, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), b.data_ptr(), None, 0,
@@ -371,10 +387,7 @@ class InferenceSnapshot:
         kernels take the logits as a strided slice of it).  ``x``: the observation already in ``self.dtype`` (written
         by the step kernel that produced it, brl_macro_ext.obs_cast) — then ``obs`` is not read.  ``raw``: the matrix in
         ``self.dtype`` as the GEMM wrote it (brl_policy_step_ex converts while reading: brl_macro_ext.in_fmt)."""
-        if x is None:
-            x = self._input(obs)
-        x = self._body(x)
-        out = torch.addmm(self.head_b, x, self.head_w)
+        out = torch.addmm(self.head_b, self.hidden(obs, x), self.head_w)
         return out if raw else out.float()
 
     def __call__(self, obs):

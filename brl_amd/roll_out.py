@@ -177,11 +177,11 @@ class _PolicyRollout:
             self.snap_opp = self.snap_actor if opp_params is params \
                 else InferenceSnapshot.make(opp_params, self.infer_dtype, self.env, own_cast=False, gemm=self.gemm)
         self.params, self.opp_params = params, opp_params
-        # fp32 inference whose every forward runs on brl_linear_x3p (models.InferenceSnapshot.planes_for): the step kernels write each new
-        # observation as bf16 instead of fp32 (0 / 1: exact) — the first layer then reads ONE plane and multiplies three products
+        # the step kernels write each new observation in the dtype the networks' layers take it in (InferenceSnapshot.input_dtype):
+        # bf16 (0 / 1: exact) where EVERY forward runs on brl_linear_x3p — the first layer then reads one plane, three products
         consumers = [self.snap_actor] + ([self.snap_opp] if self.game_mode == "competitive" else [])
         want = self.infer_dtype or torch.float32
-        if self.infer_dtype is None and all(sn is not None and sn.planes_for(self.n) for sn in consumers):
+        if all(sn is not None and sn.input_dtype(self.n) == torch.bfloat16 for sn in consumers):
             want = torch.bfloat16
         if getattr(self, "xin", None) is not None and self.xin.dtype != want:
             if self.graphs is not None:
@@ -198,19 +198,6 @@ class _PolicyRollout:
             and os.environ.get("BRL_TABLES_PER_WAVE", "4") == "4"
         return snap if ok else None
 
-    def _heads_input(self, snap, obs, x):
-        """what the step kernel forms the heads from: partial products of the last hidden layer's launch (the library's own
-        layer kernel) or, failing that, the last hidden layer itself"""
-        parts = snap.head_parts(obs, x)
-        return parts if parts is not None else snap.hidden(obs, x)
-
-    def _head_ext(self, snap, h, **kw):
-        if h.dim() == 3:   # [parts, n, ld] fp32 partial products (models.InferenceSnapshot.head_parts)
-            return _capi.MacroExt(head_part=h.data_ptr(), head_part_stride=h.stride(0), head_part_ld=h.stride(1),
-                                  head_nparts=h.shape[0], head_b=snap.head_bf.data_ptr(), **kw)
-        return _capi.MacroExt(head_h=h.data_ptr(), head_ldh=h.stride(0), head_w=snap.head_wt.data_ptr(), head_b=snap.head_bf.data_ptr(),
-                              head_hidden=h.shape[1], head_fmt=self._FMT[h.dtype], **kw)
-
     def _forward(self, is_opp, obs_bool, x=None):
         """-> f32 [n, 39] heads (38 logits + value; DeepMind ReLU nets: fused epilogues, merged heads) or, for the other
         architectures, (logits, value).  ``x``: obs_bool already cast by the step kernel."""
@@ -225,6 +212,28 @@ class _PolicyRollout:
             lg, v = fp.apply(pr, obs_bool.to(self.infer_dtype) if x is None else x)
         return lg.float(), v.float()
 
+    def _policy_input(self, is_opp, obs, x, **kw):
+        """-> (logits | None, value | None, ext): what one sub-step launch takes from the network whose turn it is, for the observation
+        `obs` (bool) or its cast `x`; `kw`: further fields of ``ext``.  Fused heads: no logits — the step kernel forms them and the
+        value itself (no N = 39 GEMM) from what ``ext`` points at and keeps alive; else the GEMM's, converted while read (in_fmt)."""
+        MX, F = _capi.MacroExt, self._FMT
+        kw.update(obs_cast=self.xin.data_ptr(), obs_fmt=F[self.xin.dtype])   # every launch casts the new observation
+        if is_opp and self.game_mode != "competitive":                  # free-run: opponents pass (src/utils.py:205-246)
+            return _pass_logits(self.env, self.n), None, MX(**kw)
+        snap = self._fused_heads(is_opp)
+        if snap is None:
+            logits, value = self._forward(is_opp, obs, x)
+            return logits, value, MX(in_fmt=F[logits.dtype], **kw)
+        h = snap.head_parts(obs, x)
+        if h is not None:   # [parts, n, ld] fp32 partial products of the last hidden layer's launch
+            ext = MX(head_part=h.data_ptr(), head_part_stride=h.stride(0), head_part_ld=h.stride(1), head_nparts=h.shape[0], **kw)
+        else:               # the stored last hidden layer itself
+            h = snap.hidden(obs, x)
+            ext = MX(head_h=h.data_ptr(), head_ldh=h.stride(0), head_w=snap.head_wt.data_ptr(), head_hidden=h.shape[1],
+                     head_fmt=F[h.dtype], **kw)
+        ext.head_b, ext.keep = snap.head_bf.data_ptr(), h      # (keep: a Python attribute — the structure holds addresses only)
+        return None, None, ext
+
     # ---- one scan step ------------------------------------------------------------------------------------------
     def _macro_step(self, t):
         """Per macro-step: 4 forwards + 4 ``brl_policy_step_ex`` launches and nothing else — value copy, accumulator reset,
@@ -232,46 +241,22 @@ class _PolicyRollout:
         env, traj, packed, cur = self.env, self.traj, self.packed, self.cur
         racc, tacc, T = self.racc, self.tacc, self.T
         competitive = self.game_mode == "competitive"
-        MX = _capi.MacroExt
-        fmt = self._FMT[self.xin.dtype]
         actor = cur[t & 1]                                              # src/roll_out.py:72
-        # the first forward of a rollout reads the loaded observation; later ones the cast written by the previous launch
-        mode1 = SAMPLE if self.masked else SAMPLE | UNMASKED
-        snap = self._fused_heads(False)
-        if snap is not None:   # the step kernel forms logits + value from the last hidden layer itself (no N = 39 GEMM)
-            h = self._heads_input(snap, traj.obs[t], None if t == 0 else self.xin)
-            policy_step(env, packed, packed, None, mode1, 4 * t, True, action=traj.action[t], log_prob=traj.log_prob[t],
-                        rewards_acc=racc, terminated_acc=tacc, draw_base=self.draw,
-                        ext=self._head_ext(snap, h, first=1, value_out=traj.value[t].data_ptr(), obs_cast=self.xin.data_ptr(),
-                                           obs_fmt=fmt))
-        else:
-            logits, value = self._forward(False, traj.obs[t], None if t == 0 else self.xin)   # :73-76
-            ifmt = self._FMT[logits.dtype]
-            # sub-step 1: the actor samples from the (un)masked Categorical (src/roll_out.py:27-39,79-84)
-            policy_step(env, packed, packed, logits, mode1, 4 * t, True,
-                        action=traj.action[t], log_prob=traj.log_prob[t], rewards_acc=racc,
-                        terminated_acc=tacc, draw_base=self.draw,
-                        ext=MX(first=1, value_in=value.data_ptr(), value_stride=value.stride(0), value_out=traj.value[t].data_ptr(),
-                               obs_cast=self.xin.data_ptr(), obs_fmt=fmt, in_fmt=ifmt))
+        # sub-step 1: the actor samples from the (un)masked Categorical (src/roll_out.py:27-39,73-84).  The first forward of a
+        # rollout reads the loaded observation; later ones the cast written by the previous launch
+        logits, value, ext = self._policy_input(False, traj.obs[t], None if t == 0 else self.xin, first=1,
+                                                value_out=traj.value[t].data_ptr())
+        if value is not None:
+            ext.value_in, ext.value_stride = value.data_ptr(), value.stride(0)
+        policy_step(env, packed, packed, logits, SAMPLE if self.masked else SAMPLE | UNMASKED, 4 * t, True, action=traj.action[t],
+                    log_prob=traj.log_prob[t], rewards_acc=racc, terminated_acc=tacc, draw_base=self.draw, ext=ext)
         last = t + 1 == T
         obs_out = self.final_obs if last else traj.obs[t + 1]
         mask_out = self.final_mask if last else traj.legal_action_mask[t + 1]
         for k in (1, 2, 3):  # opp, partner (actor params), opp — src/utils.py:78-120; always masked
-            is_opp = k != 2
-            snap = None
-            if not competitive and is_opp:                              # free-run: opponents pass (src/utils.py:205-246)
-                lg, m = _pass_logits(env, self.n), MODE
-            else:
-                m = SAMPLE if competitive else MODE
-                snap = self._fused_heads(is_opp)
-                if snap is not None:
-                    lg = None
-                    hk = self._heads_input(snap, None, self.xin)
-                else:
-                    lg, _ = self._forward(is_opp, None, self.xin)  # (the observation comes as the cast the previous launch wrote)
+            lg, _, ext = self._policy_input(k != 2, None, self.xin)
+            m = SAMPLE if competitive else MODE
             fin = k == 3
-            ext = self._head_ext(snap, hk, obs_cast=self.xin.data_ptr(), obs_fmt=fmt) if snap is not None \
-                else MX(obs_cast=self.xin.data_ptr(), obs_fmt=fmt, in_fmt=self._FMT[lg.dtype])
             if fin:                                                     # G2 / G1 / :85 by the same launch
                 ext.last, ext.done_out, ext.reward_out = 1, traj.done[t].data_ptr(), traj.reward[t].data_ptr()
                 # (terminated_count: NOT through the launch — 2048 waves adding to one address cost the last sub-step 20 us of

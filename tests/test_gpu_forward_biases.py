@@ -145,6 +145,7 @@ def test_fp32_snapshot_backends_add_every_bias(env, model, backend, monkeypatch)
     given = obs.to(torch.bfloat16) if backend == "planes_bf16" else obs
     x = snap._input(given)
     assert x.dtype == (torch.bfloat16 if backend.startswith("planes") else torch.float32)
+    assert snap.route(x) == {"library": "library", "views": "library", "x3": "x3"}.get(backend, "planes")
     with torch.no_grad():
         out = snap.heads(given)
     assert out.dtype == torch.float32 and out.shape == (n, 39)
