@@ -167,6 +167,7 @@ def lib() -> C.CDLL:
     sigs.update(review_argtypes())
     sigs.update(belief_argtypes())
     sigs.update(belief_smc_argtypes())
+    sigs.update(compare_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -262,6 +263,16 @@ def belief_smc_argtypes() -> dict:
         "brl_belief_resample": [i32, _vp, i64, _vp, i64, i64, u64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "brl_belief_propose": [i32, _vp, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp],
         "brl_belief_accept": [i32, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    }
+
+
+def compare_argtypes() -> dict:
+    """argtypes of include/brl_compare.h (the system diff; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_compare_tables": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+        "brl_compare_rows": [i32, _vp, i64, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+        "brl_compare_reduce": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
     }
 
 

@@ -6,6 +6,7 @@
                            [review=1] [review_depth=12] [save_review=review.json]
                            [belief_board=ID belief_table=a belief_call=t] [belief_samples=4096] [save_belief=belief.json]
                            [belief_resample=N] [belief_moves=2]
+                           [diff=1] [diff_depth=4] [diff_min_count=20] [save_diff=diff.json]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -25,6 +26,12 @@ three hands look like to it according to the two loaded teams, from ``belief_sam
 lines; ``save_belief`` writes it as JSON (``belief.HandBelief.from_json`` reads it back).  ``belief_resample=N`` (with
 ``belief_moves=M`` Metropolis moves per particle, default 2) resamples the deals after every N-th call a hidden seat made
 (``make_hand_belief``'s ``resample_every``): for prefixes that leave plain weighting with a handful of deals.
+``diff=1``: the system diff of the match (``compare.make_policy_diff``): team 1's network (X) and team 2's (Y) are both shown
+every decision of the first ``diff_depth`` calls of both tables' auctions — the same hand, the same auction — and the lines behind
+the ``IMP:`` line say how often they would call the same, how far apart their policies are (Jensen-Shannon, overall and by call
+index), how often each calls what was played, the largest confusion cells and the prefix with at least ``diff_min_count``
+decisions that differs most; ``save_diff`` (which implies ``diff=1``) writes the whole diff as JSON
+(``compare.PolicyDiff.from_json`` reads it back).
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -38,6 +45,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     review=0, review_depth=12, save_review=None,
     belief_board=None, belief_table="a", belief_call=0, belief_samples=4096, save_belief=None,
     belief_resample=0, belief_moves=2,
+    diff=0, diff_depth=4, diff_min_count=20, save_diff=None,
 )
 
 
@@ -50,8 +58,9 @@ def main(argv, log=print):
     if not cfg["team1_model_path"] or not cfg["team2_model_path"]:
         raise SystemExit("team1_model_path= and team2_model_path= are required")
     review = bool(cfg["review"]) or cfg["save_review"] is not None
+    diff = bool(cfg["diff"]) or cfg["save_diff"] is not None
     boards_run = (cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
-                  or review or cfg["belief_board"] is not None)
+                  or review or cfg["belief_board"] is not None or diff)
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -94,6 +103,16 @@ def main(argv, log=print):
         if cfg["save_review"] is not None:
             rv.to_json(cfg["save_review"])
             log(f"review: {cfg['save_review']}")
+    if diff:
+        from .compare import make_policy_diff
+        policy_diff = make_policy_diff(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                       cfg["team2_model_type"], depth=int(cfg["diff_depth"]))
+        pd = policy_diff(team1, team2, records)
+        for line in pd.stats_lines(min_count=int(cfg["diff_min_count"])):
+            log(line)
+        if cfg["save_diff"] is not None:
+            pd.to_json(cfg["save_diff"])
+            log(f"diff: {cfg['save_diff']}")
     if cfg["belief_board"] is not None:
         import numpy as np
 
