@@ -168,6 +168,7 @@ def lib() -> C.CDLL:
     sigs.update(belief_argtypes())
     sigs.update(belief_smc_argtypes())
     sigs.update(compare_argtypes())
+    sigs.update(crossplay_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -273,6 +274,14 @@ def compare_argtypes() -> dict:
         "brl_compare_tables": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
         "brl_compare_rows": [i32, _vp, i64, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
         "brl_compare_reduce": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+    }
+
+
+def crossplay_argtypes() -> dict:
+    """argtypes of include/brl_crossplay.h (cross-play's route; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_xplay_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
     }
 
 

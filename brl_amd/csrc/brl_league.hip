@@ -11,22 +11,19 @@
 #include "abi_common.hpp"
 #include "mlp_gemm.hpp"
 #include "mlp_rows.hpp"
+#include "route_common.hpp"
 
 namespace {
 
 using namespace mlp_rows;
+using route::board_acts;
 
 // ---- route -------------------------------------------------------------------------------------------------------------------------
 constexpr int RW = 4;   // waves (= order slots) per workgroup of the count and scatter kernels
 
-__device__ __forceinline__ bool board_acts(const uint8_t *terminated, const int32_t *current_player, int64_t b, int team) {
-  return terminated[b] == 0 && (current_player[b] >> 1) == team;
-}
-
 // the match of slot k (clamped into the batch: a bad `order` can make the result wrong, never an address)
 __device__ __forceinline__ int64_t slot_match(const int32_t *order, int64_t k, int64_t nmatch) {
-  const int64_t m = order[k];
-  return m < 0 ? 0 : (m < nmatch ? m : nmatch - 1);
+  return route::clamp_index(order[k], nmatch);
 }
 
 // work[k] = acting boards of slot k's match: one wave per slot, 64 boards per ballot
@@ -65,8 +62,7 @@ __global__ __launch_bounds__(1024) void k_route_scan(const int32_t *group_of, in
     __syncthreads();
   }
   auto group = [&](int64_t k) {
-    const int g = group_of[k];
-    return g < 0 ? 0 : (g < ngroups ? g : ngroups - 1);
+    return (int)route::clamp_index(group_of[k], ngroups);
   };
   int pos = part[tid] - c;
   for (int64_t k = a; k < b; k++) {
