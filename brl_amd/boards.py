@@ -436,19 +436,47 @@ class BoardRecords:
 
 
 # ---- a match with its boards ------------------------------------------------------------------------------------------------------
+class _KeepA:
+    """Table A's final states of a run of boards, and the records of both tables at the end.  Table B's records are taken from the
+    final states.  Table A's cannot be: the launch that ends table A re-deals the slot for table B, so its final state never
+    reaches memory.  ``brl_board_keep_a`` — one launch behind every step (``after_step``) — keeps it: the state before the step,
+    stepped with the call the loop made, by the same device function."""
+
+    def __init__(self, packed, table_a):
+        import torch
+
+        from . import _capi
+        self.packed, self.table_a = packed, table_a
+        self.prev, self.final_a = packed.clone(), torch.zeros_like(packed)
+        self.taken = torch.zeros(packed.shape[0], dtype=torch.uint8, device=packed.device)
+        self.di = _capi.device_index(packed)
+
+    def after_step(self, action):
+        from . import _capi
+        _capi.check(_capi.lib().brl_board_keep_a(self.di, _capi.ptr(self.packed), _capi.ptr(self.prev), _capi.ptr(action),
+                                                 _capi.ptr(self.table_a.terminated), _capi.ptr(self.taken), _capi.ptr(self.final_a),
+                                                 self.packed.shape[0], _capi.stream(self.di)))
+
+    def records(self, who, dda, cum, n, board_id=None):
+        """one ``BoardRecords`` per match of n boards (``cum`` [matches, n]); ``who``: the caller, named in the error"""
+        if not bool(self.taken.all()):
+            raise RuntimeError(f"{who}: a board's table A never ended")
+        rec_a, rec_b = board_records(self.final_a), board_records(self.packed)
+        imp = board_imp(rec_a, rec_b)
+        return [BoardRecords(rec_a[s:s + n], rec_b[s:s + n], imp[s:s + n], dda, board_id, cum[s // n])
+                for s in range(0, self.packed.shape[0], n)]
+
+
 def make_board_match(eval_env, team1_activation, team1_model_type, team2_activation, team2_model_type, num_eval_envs=None):
     """``board_match(team1_params, team2_params, deals | rng_key) -> (log, BoardRecords)``: ``make_simple_duplicate_evaluate``'s
     match — the same loop (``evaluation._eval_loop``), the same ``log`` = (mean IMP, standard error, win rate) bit for bit for
     the same key — and the records of both tables of every board.  With a ``Deals`` the given boards are played
     (``num_eval_envs`` is their number; every board seats players 0, 1, 2, 3 at N, E, S, W at table A).
 
-    Table B's records are taken from the final states.  Table A's cannot be: the launch that ends table A re-deals the slot for
-    table B, so its final state never reaches memory.  ``brl_board_keep_a`` — one launch behind every step — keeps it: the state
-    before the step, stepped with the call the loop made, by the same device function.  Runs on one rank."""
+    Table A's final states are kept by ``_KeepA``, one launch behind every step.  Runs on one rank."""
     import torch
     import torch.distributed as dist
 
-    from . import _capi
     from .duplicate import Table_info
     from .evaluation import _eval_loop, _match_stats, _team_forwards
     from .models import make_forward_pass
@@ -474,22 +502,11 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
             table_a_info, table_b_info = Table_info.from_state(state), Table_info.from_state(state)
             cum_return = torch.zeros(n, dtype=torch.float32, device=dev)
             fwd1, fwd2 = _team_forwards(fp1, team1_params, fp2, team2_params)
-            prev = state.packed.clone()
-            final_a = torch.zeros_like(prev)
-            taken = torch.zeros(n, dtype=torch.uint8, device=dev)
-            L, di = _capi.lib(), _capi.device_index(prev)
-
-            def keep_a(packed, action):
-                _capi.check(L.brl_board_keep_a(di, _capi.ptr(packed), _capi.ptr(prev), _capi.ptr(action),
-                                               _capi.ptr(table_a_info.terminated), _capi.ptr(taken), _capi.ptr(final_a), n,
-                                               _capi.stream(di)))
-
-            final, _ = _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None, after_step=keep_a)
+            keep = _KeepA(state.packed, table_a_info)   # (_eval_loop advances state.packed in place)
+            _eval_loop(eval_env, state, fwd1, fwd2, (table_a_info, table_b_info), None, 0, cum_return, None,
+                       after_step=lambda packed, action: keep.after_step(action))
             log = _match_stats(cum_return, n)
-            if not bool(taken.all()):
-                raise RuntimeError("board_match: a board's table A never ended")
-            rec_a, rec_b = board_records(final_a), board_records(final.packed)
-            records = BoardRecords(rec_a, rec_b, board_imp(rec_a, rec_b), dda, board_id, cum_return)
+            records, = keep.records("board_match", dda, cum_return[None], n, board_id)
         return log, records
 
     return board_match

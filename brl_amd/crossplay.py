@@ -8,11 +8,9 @@ network ``params_list[pk]``: every call of player k is that network's masked arg
 team 2; the league's match (i, j) is the line-up (i, i, j, j), bit for bit.  ``cross_play`` plays the M x M line-ups (x, y, o, o)
 against one opponent o on the same boards and reports what a pair loses by not sharing a system (``CrossPlay.gap``).
 
-A batch of P line-ups of n boards is the league's batch (match-major, every match on the SAME n boards).  Per iteration:
-
-1. ``brl_xplay_route``: the boards whose team acts, grouped by the network of the PLAYER to call (slot = (match, half),
-   half = ``current_player & 1``);
-2. ``brl_league_forward``, 3. ``brl_eval_step_team``, 4. ``_DoneWatch`` — the league's, unchanged.
+A batch of P line-ups of n boards is the league's batch (match-major, every match on the SAME n boards), played by the league's
+driver (``_match_batch.play_batches``) with ``brl_xplay_route``: the boards whose team acts are grouped by the network of the
+PLAYER to call (slot = (match, half), half = ``current_player & 1``).
 
 ``method="loop"`` plays one line-up at a time: the acting team's logits are ``where(half == 0, f_a(obs), f_b(obs))`` of its two
 players' networks (one forward when they share one): FAIR networks, mixed architectures and the timing baseline.
@@ -28,8 +26,9 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import NUM_ACTIONS, OBS_SIZE, check, device_index, ptr, stream
-from .league import LDO, LEAGUE_DEFAULTS, _net_record, _not_batchable, batch_plan, select_checkpoints
+from ._capi import NUM_ACTIONS, OBS_SIZE, check, ptr, stream
+from ._match_batch import Route, new_record, per_match_stats, play_batches
+from .league import LEAGUE_DEFAULTS, _not_batchable, batch_plan, select_checkpoints
 
 CROSSPLAY_DEFAULTS = dict(   # the league's names and defaults where the names coincide
     models_directory=LEAGUE_DEFAULTS["models_directory"], exp_name=LEAGUE_DEFAULTS["exp_name"], opp_model_path="",
@@ -62,6 +61,9 @@ def lineup_order(lineups, team: int):
     order = np.argsort(keys, kind="stable")
     nets, inverse = np.unique(keys, return_inverse=True)
     return order.astype(np.int32), inverse.reshape(-1)[order].astype(np.int32), nets.astype(np.int64)
+
+
+XPLAY_ROUTE = Route("brl_xplay_route", 2, lineup_order)   # a slot is (match, half): the acting boards by their player's network
 
 
 def cross_lineups(num_models: int):
@@ -135,31 +137,6 @@ class CrossPlay:
 # ---------------------------------------------------------------------------------------------------------------
 # the evaluation
 # ---------------------------------------------------------------------------------------------------------------
-class _KeepA:
-    """table A's final states of a run of boards (``brl_board_keep_a`` behind every step launch, as ``make_board_match``) and the
-    records of both tables at the end"""
-
-    def __init__(self, packed, table_a):
-        self.packed, self.table_a = packed, table_a
-        self.prev, self.final_a = packed.clone(), torch.zeros_like(packed)
-        self.taken = torch.zeros(packed.shape[0], dtype=torch.uint8, device=packed.device)
-        self.di = device_index(packed)
-
-    def after_step(self, action):
-        check(_capi.lib().brl_board_keep_a(self.di, ptr(self.packed), ptr(self.prev), ptr(action), ptr(self.table_a.terminated),
-                                           ptr(self.taken), ptr(self.final_a), self.packed.shape[0], stream(self.di)))
-
-    def records(self, dda, cum, n):
-        """one BoardRecords per match of n boards"""
-        from .boards import BoardRecords, board_imp, board_records
-        if not bool(self.taken.all()):
-            raise RuntimeError("lineup_evaluate: a board's table A never ended")
-        rec_a, rec_b = board_records(self.final_a), board_records(self.packed)
-        imp = board_imp(rec_a, rec_b)
-        return [BoardRecords(rec_a[s:s + n], rec_b[s:s + n], imp[s:s + n], dda, None, cum[s // n])
-                for s in range(0, self.packed.shape[0], n)]
-
-
 def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_boards=65536, method="batched", record=None,
                          boards=False):
     """-> ``lineup_evaluate(params_list, lineups, rng_key) -> (imp[P], se[P], win_rate[P], cum_return[P, n])``: match p seats
@@ -172,6 +149,7 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
     ``table_b`` and per iteration ``action``, ``rows``, ``group_first`` (batched only) and ``logits`` when ``record["logits"]``
     is true.  ``boards=True``: additionally returns one ``BoardRecords`` per line-up (both tables, IMP, ``dda``) — what
     ``system_book(records)`` reads to show what a call means in THAT partnership.  Runs on one rank."""
+    from .boards import _KeepA
     from .duplicate import Table_info
     from .evaluation import _DoneWatch, _Forward
     from .models import make_forward_pass
@@ -182,14 +160,6 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
     batch_plan(1, n, max_boards)   # (max_boards below one match: an error now, not at the first call)
     dev = eval_env.device
     lib = _capi.lib()
-
-    def new_record(first, last, tables):
-        if record is None:
-            return None
-        rec = {"matches": (first, last), "table_a": tables[0], "table_b": tables[1], "action": [], "rows": [], "group_first": [],
-               "logits": []}
-        record.setdefault("batches", []).append(rec)
-        return rec
 
     def play_loop(params_list, lineups, rng_key, cum, out_records):
         fwds = {}
@@ -205,7 +175,7 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
             dda = state._dds_tricks
             action = torch.empty(n, dtype=torch.int32, device=dev)
             keep = _KeepA(packed, tables[0]) if boards else None
-            rec = new_record(p, p + 1, tables)
+            rec = new_record(record, p, p + 1, tables)
             watch = _DoneWatch.take(eval_env, n, False)
             i = 0
             while True:
@@ -234,67 +204,7 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
                 watch.post(i, term)
                 i += 1
             if keep is not None:
-                out_records.extend(keep.records(dda, cum[p:p + 1], n))
-
-    def play_batched(refs, lineups, rng_key, cum, out_records):
-        nlayers, hidden, act = int(refs[0].nlayers), int(refs[0].hidden), int(refs[0].act)
-        net_records = np.array([_net_record(r) for r in refs], np.int64).reshape(len(refs), 20)
-        state0 = eval_env.init(rng_key, num_envs=n)                 # the n boards, dealt once
-        table0 = Table_info.from_state(state0)
-        obs0, term0, cur0, dda = state0.observation, state0.terminated, state0.current_player, state0._dds_tricks
-        di = device_index(state0.packed)
-        for first, last in batch_plan(len(lineups), n, max_boards):
-            nb = last - first
-            B = nb * n
-            packed = state0.packed.repeat(nb, 1)
-            tables = tuple(Table_info(*(t.repeat((nb,) + (1,) * (t.dim() - 1)) for t in table0)) for _ in range(2))
-            pa, pb = tables[0]._ptrs(), tables[1]._ptrs()
-            obs = [obs0.repeat(nb, 1), torch.empty((B, OBS_SIZE), dtype=torch.bool, device=dev)]
-            term, cur = term0.repeat(nb), cur0.repeat(nb)
-            cumb = cum[first:last].view(-1)
-            out = torch.zeros((B, LDO), dtype=torch.float32, device=dev)
-            action = torch.empty(B, dtype=torch.int32, device=dev)
-            rows = torch.zeros(B, dtype=torch.int64, device=dev)
-            work = torch.empty(4 * nb, dtype=torch.int32, device=dev)
-            scratch = torch.empty(B * (OBS_SIZE + 2 * hidden), dtype=torch.float32, device=dev)
-            teams = []
-            for t in (0, 1):   # the static part of a team's iterations: its order of the slots and its table of networks
-                order, group_of, nets = lineup_order(lineups[first:last], t)
-                teams.append((torch.from_numpy(order).to(dev), torch.from_numpy(group_of).to(dev),
-                              torch.from_numpy(net_records[nets].copy()).to(dev), len(nets),
-                              torch.zeros(len(nets) + 1, dtype=torch.int32, device=dev)))
-            keep = _KeepA(packed, tables[0]) if boards else None
-            rec = new_record(first, last, tables)
-            watch = _DoneWatch.take(eval_env, B, False)
-            i, rmax = 0, B
-            while True:
-                polled = watch.poll(i)
-                if polled is not None:
-                    if polled[0] >= B:
-                        watch.release()
-                        break
-                    rmax = min(rmax, B - polled[0])   # boards finish and never restart: a bound of the rows that can act
-                t = i & 1
-                order, group_of, nets, G, gf = teams[t]
-                check(lib.brl_xplay_route(di, ptr(term), ptr(cur), t, n, ptr(order), ptr(group_of), nb, G, ptr(work), ptr(rows),
-                                          ptr(gf), stream()))
-                check(lib.brl_league_forward(di, ptr(nets), G, nlayers, hidden, act, ptr(obs[i & 1]), ptr(rows), ptr(gf), rmax,
-                                             ptr(scratch), scratch.numel(), ptr(out), LDO, stream()))
-                if rec is not None and record.get("logits"):
-                    rec["logits"].append(out.clone())
-                check(lib.brl_eval_step_team(eval_env._h, ptr(packed), ptr(packed), B, ptr(out), LDO, t, C.byref(pa), C.byref(pb),
-                                             None, 0, ptr(cumb), None, ptr(action), ptr(obs[(i & 1) ^ 1]), None, None, ptr(term),
-                                             ptr(cur), None, stream()))
-                if keep is not None:
-                    keep.after_step(action)
-                if rec is not None:
-                    rec["action"].append(action.clone())
-                    rec["rows"].append(rows.clone())
-                    rec["group_first"].append(gf.clone())
-                watch.post(i, term)
-                i += 1
-            if keep is not None:
-                out_records.extend(keep.records(dda, cum[first:last], n))
+                out_records.extend(keep.records("lineup_evaluate", dda, cum[p:p + 1], n))
 
     def lineup_evaluate(params_list, lineups, rng_key):
         import torch.distributed as dist
@@ -314,17 +224,12 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
             lineup_evaluate.last_method = use
             if len(lineups):
                 if use == "batched":
-                    play_batched(refs, lineups, rng_key, cum, out_records)
+                    out_records = play_batches(eval_env, refs, lineups, XPLAY_ROUTE, eval_env.init(rng_key, num_envs=n),
+                                               batch_plan(len(lineups), n, max_boards), cum, record, boards, "lineup_evaluate")
                 else:
                     play_loop(params_list, lineups, rng_key, cum, out_records)
-            nf = float(n)
-            if not len(lineups):
-                empty = cum.new_zeros(0)
-                return (empty, empty, empty, cum, out_records) if boards else (empty, empty, empty, cum)
-            imp = cum.mean(dim=1)
-            se = cum.std(dim=1, unbiased=True) / nf ** 0.5          # src/evaluation.py:199
-            win_rate = (cum > 0).sum(dim=1) / nf                    # :200
-            return (imp, se, win_rate, cum, out_records) if boards else (imp, se, win_rate, cum)
+            stats = per_match_stats(cum, n) if len(lineups) else (cum.new_zeros(0),) * 3
+            return (*stats, cum, out_records) if boards else (*stats, cum)
 
     lineup_evaluate.last_method = None
     return lineup_evaluate

@@ -40,37 +40,11 @@ __global__ __launch_bounds__(64 * RW) void k_xroute_count(const uint8_t *termina
   }
 }
 
-// work[nslots + s] = the first row of slot s = order[k] (exclusive scan of the counts along the order), group_first[g] = the first
-// row of group g's first position (of the next group's for a group without slots), group_first[ngroups] = the total.  One
-// workgroup, k_route_scan's shape (brl_league.hip): a thread owns a run of positions, the runs' offsets come from a scan in LDS;
-// every group_first entry is written by exactly one thread (the one that owns the position where the group changes).
+// work[nslots + s] = the first row of slot s = order[k], group_first = the groups' first rows and the total: route::scan along the
+// order, on counts that k_xroute_count wrote by slot
 __global__ __launch_bounds__(1024) void k_xroute_scan(const int32_t *order, const int32_t *group_of, int64_t nslots, int ngroups,
                                                       int32_t *work, int32_t *group_first) {
-  __shared__ int part[1024];
-  const int tid = (int)threadIdx.x;
-  const int64_t per = (nslots + 1023) / 1024, a0 = (int64_t)tid * per, a = a0 < nslots ? a0 : nslots, b = a + per < nslots ? a + per : nslots;
-  auto slot = [&](int64_t k) { return route::clamp_index(order[k], nslots); };
-  auto group = [&](int64_t k) { return (int)route::clamp_index(group_of[k], ngroups); };
-  int c = 0;
-  for (int64_t k = a; k < b; k++) c += work[slot(k)];
-  part[tid] = c;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {   // inclusive scan
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int pos = part[tid] - c;
-  for (int64_t k = a; k < b; k++) {
-    const int64_t s = slot(k);
-    work[nslots + s] = pos;
-    const int g = group(k);
-    for (int gg = (k == 0) ? 0 : group(k - 1) + 1; gg <= g; gg++) group_first[gg] = pos;
-    pos += work[s];
-  }
-  if (tid == 1023)
-    for (int gg = group(nslots - 1) + 1; gg <= ngroups; gg++) group_first[gg] = part[1023];
+  route::scan<true>(order, group_of, nslots, ngroups, work, group_first);
 }
 
 // rows[first row of slot 2 m + h ..] = the boards of match m that act in half h, ascending: both halves in one pass of the match
@@ -101,10 +75,7 @@ __global__ __launch_bounds__(64 * RW) void k_xroute_scatter(const uint8_t *termi
 extern "C" int brl_xplay_route(int device, const uint8_t *terminated, const int32_t *current_player, int team, int64_t n,
                                const int32_t *order, const int32_t *group_of, int64_t nmatch, int64_t ngroups, int32_t *work,
                                int64_t *rows, int32_t *group_first, void *stream) {
-  NEED(terminated && current_player && order && group_of && work && rows && group_first, "NULL array");
-  NEED(team == 0 || team == 1, "team (0 / 1)");
-  NEED(n > 0 && nmatch > 0 && ngroups > 0, "n / nmatch / ngroups");
-  NEED(nmatch * n < ((int64_t)1 << 31) && nmatch < ((int64_t)1 << 24) && ngroups < ((int64_t)1 << 24), "nmatch * n below 2^31, nmatch and ngroups below 2^24");
+  if (int e = route::check_args(terminated, current_player, team, n, order, group_of, nmatch, ngroups, work, rows, group_first)) return e;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const unsigned blocks = (unsigned)((nmatch + RW - 1) / RW);

@@ -42,37 +42,11 @@ __global__ __launch_bounds__(64 * RW) void k_route_count(const uint8_t *terminat
   if (lane == 0) work[k] = c;
 }
 
-// work[nmatch + k] = the first row of slot k (exclusive scan of the counts), group_first[g] = the first row of group g's first slot
-// (of the next group's for a group without slots), group_first[ngroups] = the total.  One workgroup: a thread owns a run of slots,
-// the runs' offsets come from a scan in LDS; every group_first entry is written by exactly one thread (the one that owns the slot
-// where the group changes).
+// work[nmatch + k] = the first row of slot k, group_first = the groups' first rows and the total: route::scan on counts that
+// k_route_count wrote in the order already
 __global__ __launch_bounds__(1024) void k_route_scan(const int32_t *group_of, int64_t nmatch, int ngroups, int32_t *work,
                                                      int32_t *group_first) {
-  __shared__ int part[1024];
-  const int tid = (int)threadIdx.x;
-  const int64_t per = (nmatch + 1023) / 1024, a0 = (int64_t)tid * per, a = a0 < nmatch ? a0 : nmatch, b = a + per < nmatch ? a + per : nmatch;
-  int c = 0;
-  for (int64_t k = a; k < b; k++) c += work[k];
-  part[tid] = c;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {   // inclusive scan
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  auto group = [&](int64_t k) {
-    return (int)route::clamp_index(group_of[k], ngroups);
-  };
-  int pos = part[tid] - c;
-  for (int64_t k = a; k < b; k++) {
-    work[nmatch + k] = pos;
-    const int g = group(k);
-    for (int gg = (k == 0) ? 0 : group(k - 1) + 1; gg <= g; gg++) group_first[gg] = pos;
-    pos += work[k];
-  }
-  if (tid == 1023)
-    for (int gg = group(nmatch - 1) + 1; gg <= ngroups; gg++) group_first[gg] = part[1023];
+  route::scan<false>(nullptr, group_of, nmatch, ngroups, work, group_first);
 }
 
 // rows[first row of slot k ..] = the acting boards of its match, ascending
@@ -164,10 +138,7 @@ __global__ __launch_bounds__(256) void k_league_heads(const brl_league_net *nets
 extern "C" int brl_league_route(int device, const uint8_t *terminated, const int32_t *current_player, int team, int64_t n,
                                 const int32_t *order, const int32_t *group_of, int64_t nmatch, int64_t ngroups, int32_t *work,
                                 int64_t *rows, int32_t *group_first, void *stream) {
-  NEED(terminated && current_player && order && group_of && work && rows && group_first, "NULL array");
-  NEED(team == 0 || team == 1, "team (0 / 1)");
-  NEED(n > 0 && nmatch > 0 && ngroups > 0, "n / nmatch / ngroups");
-  NEED(nmatch * n < ((int64_t)1 << 31) && nmatch < ((int64_t)1 << 24) && ngroups < ((int64_t)1 << 24), "nmatch * n below 2^31, nmatch and ngroups below 2^24");
+  if (int e = route::check_args(terminated, current_player, team, n, order, group_of, nmatch, ngroups, work, rows, group_first)) return e;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const unsigned blocks = (unsigned)((nmatch + RW - 1) / RW);

@@ -5,12 +5,8 @@ learner against every pool checkpoint).
     python -m brl_amd.league models_directory=rl_log exp_name=exp_0000/rl_params skip_interval=100 [dds_path=...] [max_boards=65536]
 
 A league of P matches of n boards is one batch of P * n boards (match-major: board b belongs to match b // n) in which every
-board's call comes from one of M networks of ONE architecture.  Per iteration (the teams alternate, as in ``_eval_loop``):
-
-1. ``brl_league_route``: the boards whose team acts, grouped by the network that plays that team in their match;
-2. ``brl_league_forward``: the cast, every hidden layer and the heads as one launch each over all groups;
-3. ``brl_eval_step_team`` on the whole batch (unchanged: one logits row per board);
-4. ``_DoneWatch.post`` / ``poll`` — the only host synchronisation.
+board's call comes from one of M networks of ONE architecture, played by ``_match_batch.play_batches`` with ``brl_league_route``:
+the boards whose team acts are grouped by the network that plays that team in their match.
 
 Every match plays the SAME n boards (those of ``eval_env.init(rng_key, num_envs=n)``, dealt once and tiled), so match p gives the
 numbers of ``make_simple_duplicate_evaluate(...)(params_list[i], params_list[j], rng_key)``.  ``method="loop"`` plays the pairs
@@ -18,7 +14,6 @@ one by one through the existing evaluator's loop: FAIR networks, mixed architect
 """
 from __future__ import annotations
 
-import ctypes as C
 import itertools
 import os
 import sys
@@ -26,8 +21,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _capi
-from ._capi import OBS_SIZE, check, device_index, ptr, stream
+from ._match_batch import LDO, Route, _net_record, per_match_stats, play_batches  # noqa: F401  (LDO, _net_record: imported from here)
 
 LEAGUE_DEFAULTS = dict(  # workspace/eval_selfplay_league.py: SelfplayLeagueConfig, same names and defaults
     models_directory="models", exp_name="pretrained-rl-with-sp", num_eval_envs=100, skip_interval=100, max_step=10000,
@@ -35,8 +29,6 @@ LEAGUE_DEFAULTS = dict(  # workspace/eval_selfplay_league.py: SelfplayLeagueConf
     # build-side (not in the reference, which reads dds_results/test_000.npy)
     dds_path="dds_results/test_000.npy", max_boards=65536,
 )
-
-LDO = 40   # row stride of the logits buffer: 38 logits + the value, padded to whole 16 bytes
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -100,9 +92,7 @@ def all_pairs(num_models: int):
 # ---------------------------------------------------------------------------------------------------------------
 # the evaluation
 # ---------------------------------------------------------------------------------------------------------------
-def _net_record(ref) -> list:
-    """brl_league_net of a brl_mlp_ref: its 20 pointers"""
-    return [ref.w[i] or 0 for i in range(8)] + [ref.b[i] or 0 for i in range(8)] + [ref.actor_w, ref.actor_b, ref.critic_w, ref.critic_b]
+LEAGUE_ROUTE = Route("brl_league_route", 1, team_order)   # a slot is a match: the acting boards by their team's network
 
 
 def _not_batchable(model_type, refs):
@@ -132,7 +122,7 @@ def make_league_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
     when ``record["logits"]`` is true).  ``shard`` (evaluation._Shard): the n boards are split over the ranks; the three statistics
     are those of all boards on every rank, ``cum_return`` holds this rank's."""
     from .duplicate import Table_info
-    from .evaluation import _DoneWatch, _eval_loop, _Forward, _Shard
+    from .evaluation import _eval_loop, _Forward, _Shard
     from .models import make_forward_pass
     if method not in ("batched", "loop"):
         raise ValueError(f"method {method!r}: 'batched' or 'loop'")
@@ -140,7 +130,6 @@ def make_league_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
     n_global = int(num_eval_envs)
     batch_plan(1, n_global, max_boards)   # (max_boards below one match: an error now, not at the first league)
     dev = eval_env.device
-    lib = _capi.lib()
 
     def play_loop(params_list, pairs, rng_key, sh, cum):
         fwds = {}
@@ -151,66 +140,6 @@ def make_league_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
             state = sh.init(eval_env, rng_key)
             tables = (Table_info.from_state(state), Table_info.from_state(state))
             _eval_loop(eval_env, state, fwds[i], fwds[j], tables, None, 0, cum[p], None)
-
-    def play_batched(refs, pairs, rng_key, sh, cum):
-        n = sh.n
-        nlayers, hidden, act = int(refs[0].nlayers), int(refs[0].hidden), int(refs[0].act)
-        records = np.array([_net_record(r) for r in refs], np.int64).reshape(len(refs), 20)
-        state0 = sh.init(eval_env, rng_key)                      # the n boards, dealt once
-        table0 = Table_info.from_state(state0)
-        obs0, term0, cur0 = state0.observation, state0.terminated, state0.current_player
-        di = device_index(state0.packed)
-        for first, last in batch_plan(len(pairs), n_global, max_boards):
-            nb = last - first
-            B = nb * n
-            packed = state0.packed.repeat(nb, 1)
-            tables = tuple(Table_info(*(t.repeat((nb,) + (1,) * (t.dim() - 1)) for t in table0)) for _ in range(2))
-            pa, pb = tables[0]._ptrs(), tables[1]._ptrs()
-            obs = [obs0.repeat(nb, 1), torch.empty((B, OBS_SIZE), dtype=torch.bool, device=dev)]
-            term, cur = term0.repeat(nb), cur0.repeat(nb)
-            cumb = cum[first:last].view(-1)
-            out = torch.zeros((B, LDO), dtype=torch.float32, device=dev)
-            action = torch.empty(B, dtype=torch.int32, device=dev)
-            rows = torch.zeros(B, dtype=torch.int64, device=dev)
-            work = torch.empty(2 * nb, dtype=torch.int32, device=dev)
-            scratch = torch.empty(B * (OBS_SIZE + 2 * hidden), dtype=torch.float32, device=dev)
-            teams = []
-            for t in (0, 1):   # the static part of a team's iterations: its order of the matches and its table of networks
-                order, group_of, nets = team_order(pairs[first:last], t)
-                teams.append((torch.from_numpy(order).to(dev), torch.from_numpy(group_of).to(dev),
-                              torch.from_numpy(records[nets].copy()).to(dev), len(nets),
-                              torch.zeros(len(nets) + 1, dtype=torch.int32, device=dev)))
-            rec = None
-            if record is not None:
-                rec = {"matches": (first, last), "table_a": tables[0], "table_b": tables[1], "action": [], "rows": [],
-                       "group_first": [], "logits": []}
-                record.setdefault("batches", []).append(rec)
-            watch = _DoneWatch.take(eval_env, B, False)
-            i, rmax = 0, B
-            while True:
-                polled = watch.poll(i)
-                if polled is not None:
-                    if polled[0] >= B:
-                        watch.release()
-                        break
-                    rmax = min(rmax, B - polled[0])   # boards finish and never restart: a bound of the rows that can act
-                t = i & 1
-                order, group_of, nets, G, gf = teams[t]
-                check(lib.brl_league_route(di, ptr(term), ptr(cur), t, n, ptr(order), ptr(group_of), nb, G, ptr(work), ptr(rows),
-                                           ptr(gf), stream()))
-                check(lib.brl_league_forward(di, ptr(nets), G, nlayers, hidden, act, ptr(obs[i & 1]), ptr(rows), ptr(gf), rmax,
-                                             ptr(scratch), scratch.numel(), ptr(out), LDO, stream()))
-                if rec is not None and record.get("logits"):
-                    rec["logits"].append(out.clone())
-                check(lib.brl_eval_step_team(eval_env._h, ptr(packed), ptr(packed), B, ptr(out), LDO, t, C.byref(pa), C.byref(pb),
-                                             None, 0, ptr(cumb), None, ptr(action), ptr(obs[(i & 1) ^ 1]), None, None, ptr(term),
-                                             ptr(cur), None, stream()))
-                if rec is not None:
-                    rec["action"].append(action.clone())
-                    rec["rows"].append(rows.clone())
-                    rec["group_first"].append(gf.clone())
-                watch.post(i, term)
-                i += 1
 
     def league_evaluate(params_list, pairs, rng_key):
         pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
@@ -227,21 +156,12 @@ def make_league_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
                     use = "loop"
             league_evaluate.last_method = use
             if len(pairs):
-                if use == "batched":
-                    play_batched(refs, pairs, rng_key, sh, cum)
+                if use == "batched":   # (the plan is made from the global n; a rank tiles its own sh.n boards)
+                    play_batches(eval_env, refs, pairs, LEAGUE_ROUTE, sh.init(eval_env, rng_key),
+                                 batch_plan(len(pairs), n_global, max_boards), cum, record)
                 else:
                     play_loop(params_list, pairs, rng_key, sh, cum)
-            nf = float(n_global)
-            if sh.active:   # sums over every rank's boards (IMPs are integers: exact in float64)
-                x = cum.to(torch.float64)
-                s = sh.allsum(torch.stack([x.sum(1), (x * x).sum(1), (x > 0).sum(1).to(torch.float64)]))
-                mean = s[0] / nf
-                var = ((s[1] - nf * mean * mean) / (nf - 1.0)).clamp_min(0.0)
-                return mean.to(torch.float32), (var.sqrt() / nf ** 0.5).to(torch.float32), (s[2] / nf).to(torch.float32), cum
-            imp = cum.mean(dim=1)
-            se = cum.std(dim=1, unbiased=True) / nf ** 0.5          # src/evaluation.py:199
-            win_rate = (cum > 0).sum(dim=1) / nf                    # :200
-            return imp, se, win_rate, cum
+            return (*per_match_stats(cum, n_global, sh), cum)
 
     league_evaluate.last_method = None
     return league_evaluate

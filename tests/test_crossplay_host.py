@@ -67,6 +67,32 @@ def test_shared_partners_give_the_leagues_order_with_every_match_split_in_two():
         assert np.array_equal(group_of, np.repeat(lg, 2))                                # ... and in one group
 
 
+@pytest.mark.parametrize("P,n", [(1100, 3), (600, 3)])
+@pytest.mark.parametrize("team", [0, 1])
+def test_the_two_route_restatements_agree_on_shared_partners_beyond_1024_slots(P, n, team):
+    """the shapes at which tests/test_gpu_league.py and tests/test_gpu_crossplay.py give a thread of the scan two positions: on
+    line-ups (i, i, j, j) both restatements give one group_first and the same boards in every group; and the league's 1100 pairs
+    (the GPU test's own) change group inside a thread's run of two positions and at its end"""
+    from brl_amd.crossplay import lineup_order
+    from brl_amd.league import team_order
+    from tests.test_league_host import route_numpy
+    rng = np.random.default_rng(100 * P + n + team)
+    M = 7
+    pairs = rng.integers(0, M, (P, 2))
+    lineups = np.stack([pairs[:, 0], pairs[:, 0], pairs[:, 1], pairs[:, 1]], axis=1)
+    term = (rng.random(P * n) < 0.4).astype(np.uint8)
+    cur = rng.integers(0, 4, P * n).astype(np.int32)
+    order, group_of, nets = lineup_order(lineups, team)
+    lrows, lgf = route_numpy(term, cur, pairs, team, n, num_groups=M + 2)
+    rows, gf = xroute_numpy(term, cur, team, n, order, nets[group_of], M + 2)
+    assert np.array_equal(gf, lgf) and gf[-1] == gf[M] > 0 and sorted(rows.tolist()) == sorted(lrows.tolist())
+    for g in range(M):
+        assert np.array_equal(np.sort(rows[gf[g]:gf[g + 1]]), np.sort(lrows[gf[g]:gf[g + 1]]))
+    if P == 1100:
+        changes = np.nonzero(np.diff(team_order(pairs, team)[1]))[0] + 1  # the league's positions where a new group starts
+        assert len(changes) == M - 1 and {0, 1} == set((changes % 2).tolist())
+
+
 def test_route_restatement_on_hand_made_cases():
     from brl_amd.crossplay import lineup_order
     n = 5

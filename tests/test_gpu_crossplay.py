@@ -59,16 +59,17 @@ def _slot_boards(term, cur, team, n, slot):
     return b[(term[b] == 0) & ((cur[b] >> 1) == team) & ((cur[b] & 1) == (slot & 1))]
 
 
-@pytest.mark.parametrize("nmatch,n", [(1, 1), (1, 63), (3, 64), (3, 65), (10, 200)])
+@pytest.mark.parametrize("nmatch,n", [(1, 1), (1, 63), (3, 64), (3, 65), (10, 200), (600, 3)])
 @pytest.mark.parametrize("team", [0, 1])
 def test_route_equals_the_numpy_restatement(nmatch, n, team):
     """rows[:R] and group_first exactly, rows[R:] untouched; group id = network id with two groups that no slot names.  Cases: random
     boards; nothing acts (every board finished: R = 0); and, where the batch has three matches, a crafted one — line-up 0 seats one
     network on both halves (a match whose two players share a group), the second position of the order is emptied between two
-    non-empty ones, and every board of the last position's network is finished (a named group without an acting board)."""
+    non-empty ones, and every board of the last position's network is finished (a named group without an acting board).
+    600 matches are 1200 slots: two positions per thread of the scan."""
     from brl_amd.crossplay import lineup_order
     rng = np.random.default_rng(1000 * nmatch + 10 * n + team)
-    M = 5
+    M = 7 if nmatch == 600 else 5
     lineups = rng.integers(0, M, (nmatch, 4))
     lineups[0] = (2, 2, 2, 2)
     if nmatch >= 3:
@@ -76,6 +77,8 @@ def test_route_equals_the_numpy_restatement(nmatch, n, team):
     order, group_of, nets = lineup_order(lineups, team)
     groups = nets[group_of]                                              # group id = network id: still non-decreasing
     G = M + 2
+    if nmatch == 600:                                                    # groups change inside a thread's two positions and at their end
+        assert {0, 1} == set(((np.nonzero(np.diff(groups))[0] + 1) % 2).tolist())
     for case in ("random", "nothing acts", "crafted"):
         term = (rng.random(nmatch * n) < 0.4).astype(np.uint8)
         cur = rng.integers(0, 4, nmatch * n).astype(np.int32)
@@ -85,7 +88,7 @@ def test_route_equals_the_numpy_restatement(nmatch, n, team):
             if nmatch < 3:
                 continue
             for k in (0, 2):                                             # positions 0 and 2 of the order: at least one acting board each
-                b = (order[k] >> 1) * n + 3 + k
+                b = (order[k] >> 1) * n + (3 + k) % n
                 term[b], cur[b] = 0, 2 * team + (order[k] & 1)
             term[_slot_boards(term, cur, team, n, order[1])] = 1         # ... and none in position 1, between them
             dead = groups[-1]

@@ -43,11 +43,11 @@ def _route(term, cur, pairs, team, n, num_groups):
     return rows, gf
 
 
-@pytest.mark.parametrize("P,n", [(1, 37), (6, 100), (45, 100), (3, 1000)])
+@pytest.mark.parametrize("P,n", [(1, 37), (6, 100), (45, 100), (3, 1000), (1100, 3)])   # (1100: two slots per thread of the scan)
 @pytest.mark.parametrize("team", [0, 1])
 def test_route_equals_the_numpy_restatement(P, n, team):
     rng = np.random.default_rng(100 * P + n + team)
-    M = 1 if P == 1 else (4 if P == 6 else 10)
+    M = 1 if P == 1 else (4 if P == 6 else (7 if P == 1100 else 10))
     pairs = np.array([[0, 0]]) if P == 1 else (np.array([(i, j) for i in range(10) for j in range(i + 1, 10)]) if P == 45
                                                else rng.integers(0, M, (P, 2)))
     for case in ("random", "nothing acts"):

@@ -1,9 +1,11 @@
 """CPU checks of the league evaluation's host side (brl_amd/league.py, include/brl_league.h): the binding's argument types, the
-checkpoint filter, the three matrices, the batch plan, the per-team match orders, the CLI's parser, the trainer's default, and a
+checkpoint filter, the three matrices, the batch plan, the per-team match orders, the CLI's parser, the trainer's default, the
+matches' statistics (``_match_batch.per_match_stats``: sharded over fake ranks against numpy float64, plain against torch), and a
 numpy restatement of the route (``route_numpy``: what tests/test_gpu_league.py compares the kernels with) on hand-made cases."""
 import ctypes
 import os
 import re
+import warnings
 
 import numpy as np
 import pytest
@@ -138,6 +140,64 @@ def test_train_default_keeps_the_loop():
     from brl_amd.train import DEFAULTS, parse_cli
     assert DEFAULTS["league_eval"] == "loop"
     assert parse_cli(["league_eval=batched"])["league_eval"] == "batched"
+
+
+class _FakeRank:
+    """the two members of evaluation._Shard that per_match_stats uses.  ``stacks`` None: ``allsum`` hands this rank's stack back
+    (to collect it); a list of every rank's stack: ``allsum`` is their plain Python sum"""
+    active = True
+
+    def __init__(self, stacks=None):
+        self.stacks, self.own = stacks, None
+
+    def allsum(self, t):
+        self.own = t
+        return t if self.stacks is None else sum(self.stacks)
+
+
+@pytest.mark.parametrize("sizes", [(21, 20), (14, 14, 13), (40, 1), (1, 2, 38)])
+def test_match_statistics_sharded_and_plain(sizes):
+    """Integer-valued rows of odd length n = 41 over 2 and 3 ranks of unequal sizes.  Sharded: every rank gets the numpy float64
+    statistics of the whole rows rounded to float32.  Mean and win rate exactly: sums of integers and one division, as numpy's.
+    se within one float32 ulp (relative 2^-23): the variance is (sum of squares - n mean^2) / (n - 1) in float64, whose terms are
+    below 41 * 24^2 < 2^15 and carry a few 2^-53 relative, 1e-11 absolute at the most, against a numerator of at least
+    1 - 1 / 41 for an integer row that is not constant (row 3) — so the float64 values agree to 1e-11 relative and can only fall
+    on two neighbouring float32.  A constant row has an exact mean, its numerator is 0 (the clamp keeps what rounding could make
+    of it from becoming a NaN): se is 0.  Plain: torch's own mean / std / count, exactly as the evaluators return them."""
+    import torch
+
+    from brl_amd._match_batch import per_match_stats
+    n = sum(sizes)
+    rng = np.random.default_rng(n + len(sizes))
+    x = rng.integers(-24, 25, (6, n)).astype(np.float32)
+    x[1], x[2] = 7.0, -3.0                                   # constant rows: variance 0
+    x[3] = 0.0
+    x[3, 5] = 1.0                                            # the smallest non-zero variance of an integer row
+    x64 = x.astype(np.float64)
+    want = (x64.mean(1).astype(np.float32), (x64.std(1, ddof=1) / np.sqrt(n)).astype(np.float32), (x > 0).mean(1).astype(np.float32))
+    bounds = np.concatenate([[0], np.cumsum(sizes)])
+    parts = [torch.from_numpy(x[:, a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+    stacks = []
+    for part in parts:
+        rank = _FakeRank()
+        per_match_stats(part, n, rank)
+        stacks.append(rank.own)
+    for k, part in enumerate(parts):
+        rank = _FakeRank(stacks)
+        imp, se, win = (t.numpy() for t in per_match_stats(part, n, rank))
+        assert torch.equal(rank.own, stacks[k]) and imp.dtype == se.dtype == win.dtype == np.float32
+        assert np.array_equal(imp, want[0]) and np.array_equal(win, want[2])
+        assert np.isfinite(se).all() and (se[1:3] == 0).all() and (se[[0, 3, 4, 5]] > 0).all()
+        assert (np.abs(se - want[1]) <= 2.0 ** -23 * want[1]).all()
+    cum = torch.from_numpy(x)
+    for shard in (None, type("Idle", (), {"active": False})()):
+        imp, se, win = per_match_stats(cum, n, shard)
+        assert torch.equal(imp, cum.mean(dim=1)) and torch.equal(se, cum.std(dim=1, unbiased=True) / float(n) ** 0.5)
+        assert torch.equal(win, (cum > 0).sum(dim=1) / float(n))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                      # (torch warns about the std of nothing)
+        empty = per_match_stats(cum[:0], n)                  # a league without pairs: three empty vectors
+    assert all(t.shape == (0,) and t.dtype == torch.float32 for t in empty)
 
 
 def _case(P, n, pairs, acting):
