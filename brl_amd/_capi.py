@@ -169,6 +169,7 @@ def lib() -> C.CDLL:
     sigs.update(belief_smc_argtypes())
     sigs.update(compare_argtypes())
     sigs.update(crossplay_argtypes())
+    sigs.update(distill_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -282,6 +283,15 @@ def crossplay_argtypes() -> dict:
     i64, i32 = C.c_int64, C.c_int
     return {
         "brl_xplay_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
+    }
+
+
+def distill_argtypes() -> dict:
+    """argtypes of include/brl_distill.h (policy distillation's targets and loss head; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32, f32 = C.c_int64, C.c_int, C.c_float
+    return {
+        "brl_distill_targets": [i32, _vp, i64, i64, _vp, i64, i64, _vp, _vp, i64, i32, f32, _vp, _vp, _vp, _vp],
+        "brl_distill_loss": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp, _vp],
     }
 
 
