@@ -170,6 +170,7 @@ def lib() -> C.CDLL:
     sigs.update(compare_argtypes())
     sigs.update(crossplay_argtypes())
     sigs.update(distill_argtypes())
+    sigs.update(lines_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -292,6 +293,17 @@ def distill_argtypes() -> dict:
     return {
         "brl_distill_targets": [i32, _vp, i64, i64, _vp, i64, i64, _vp, _vp, i64, i32, f32, _vp, _vp, _vp, _vp],
         "brl_distill_loss": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp, _vp],
+    }
+
+
+def lines_argtypes() -> dict:
+    """argtypes of include/brl_lines.h (the auction lines' beam search; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_lines_init": [i32, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "brl_lines_expand": [i32, _vp, _vp, _vp, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "brl_lines_finish": [i32, _vp, _vp, i64, _vp, _vp],
+        "brl_lines_imp": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, i32, _vp, _vp],
     }
 
 

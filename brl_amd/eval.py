@@ -7,6 +7,7 @@
                            [belief_board=ID belief_table=a belief_call=t] [belief_samples=4096] [save_belief=belief.json]
                            [belief_resample=N] [belief_moves=2]
                            [diff=1] [diff_depth=4] [diff_min_count=20] [save_diff=diff.json]
+                           [lines=K] [lines_max_calls=64] [save_lines=lines.json]
 
 The two teams may differ in type, so this is ``make_simple_duplicate_evaluate`` (a league of one architecture is
 ``python -m brl_amd.league``).  rng key 0, as in the reference.  Prints ``IMP: mean ± standard error``.
@@ -32,6 +33,11 @@ the ``IMP:`` line say how often they would call the same, how far apart their po
 index), how often each calls what was played, the largest confusion cells and the prefix with at least ``diff_min_count``
 decisions that differs most; ``save_diff`` (which implies ``diff=1``) writes the whole diff as JSON
 (``compare.PolicyDiff.from_json`` reads it back).
+``lines=K`` (1 .. 16): the auction lines of the same boards (``lines.make_auction_lines``): a beam search of width K over the
+auctions of both tables under the two teams' masked softmax, at most ``lines_max_calls`` calls deep; the lines behind the other
+lines give the expected IMP of the policies as trained with its bound (24 x the mass not covered), the covered mass, how much of
+its policy's mass the greedy auction carries and how often another auction is more probable; ``save_lines`` (which needs
+``lines=K``) writes every line as JSON (``lines.AuctionLines.from_json`` reads it back).
 Without these arguments the output is what it always was."""
 from __future__ import annotations
 
@@ -46,6 +52,7 @@ EVAL_DEFAULTS = dict(  # eval.py: EVALConfig, same names and defaults
     belief_board=None, belief_table="a", belief_call=0, belief_samples=4096, save_belief=None,
     belief_resample=0, belief_moves=2,
     diff=0, diff_depth=4, diff_min_count=20, save_diff=None,
+    lines=0, lines_max_calls=64, save_lines=None,
 )
 
 
@@ -61,6 +68,9 @@ def main(argv, log=print):
     diff = bool(cfg["diff"]) or cfg["save_diff"] is not None
     boards_run = (cfg["deals_path"] is not None or cfg["save_boards"] is not None or cfg["save_book"] is not None or bool(cfg["par"])
                   or review or cfg["belief_board"] is not None or diff)
+    beam = int(cfg["lines"])
+    if beam < 0 or beam > 16 or (cfg["save_lines"] is not None and beam == 0):
+        raise SystemExit("lines=K: 1 .. 16 (0: no lines); save_lines= needs lines=K")
     deals = None
     if cfg["deals_path"] is not None:
         from .boards import read_deals
@@ -134,6 +144,16 @@ def main(argv, log=print):
         if cfg["save_belief"] is not None:
             hb.to_json(cfg["save_belief"])
             log(f"belief: {cfg['save_belief']}")
+    if beam:
+        from .lines import make_auction_lines
+        auction_lines = make_auction_lines(env, cfg["team1_activation"], cfg["team1_model_type"], cfg["team2_activation"],
+                                           cfg["team2_model_type"], cfg["num_eval_envs"], k=beam, max_calls=int(cfg["lines_max_calls"]))
+        al = auction_lines(team1, team2, deals if deals is not None else 0)
+        for line in al.summary_lines():
+            log(line)
+        if cfg["save_lines"] is not None:
+            al.to_json(cfg["save_lines"])
+            log(f"lines: {cfg['save_lines']}")
     return float(imp), float(se)
 
 
