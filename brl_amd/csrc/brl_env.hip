@@ -348,6 +348,7 @@ extern "C" int brl_init_from_deals(brl_handle *h, uint64_t *state, int64_t n, co
 extern "C" int brl_step(brl_handle *h, const uint64_t *state_in, uint64_t *state_out, int64_t n,
                         const int32_t *action, int autoreset, uint8_t *obs, uint8_t *mask, float *rewards,
                         uint8_t *terminated, int32_t *current_player, void *stream) {
+  NEED(step_outputs_aligned(state_in, state_out, obs, rewards, action, current_player), STEP_ALIGN_MSG);
   COMMON(h, n);
   NEED(state_in && state_out && action, "NULL state / action");
   if (autoreset && h->lut_len == 0) return fail(BRL_E_NOLUT, "auto-reset needs a LUT%s", "");
@@ -358,6 +359,7 @@ extern "C" int brl_step(brl_handle *h, const uint64_t *state_in, uint64_t *state
 
 extern "C" int brl_observe(brl_handle *h, const uint64_t *state, int64_t n, const int32_t *player_id, uint8_t *obs,
                            uint8_t *mask, void *stream) {
+  NEED(step_outputs_aligned(state, nullptr, obs, nullptr, player_id, nullptr), STEP_ALIGN_MSG);
   COMMON(h, n);
   NEED(state != nullptr, "state");
   LAUNCH_K(h, k_observe, n, stream, state, n, player_id, obs, mask);

@@ -56,6 +56,7 @@ __global__ __launch_bounds__(256) void k_obs_cast_rows(const uint4 *in, const in
 }
 
 extern "C" int brl_obs_cast(brl_handle *h, const uint8_t *obs, int64_t n, void *out, int fmt, void *stream) {
+  NEED((((uintptr_t)obs | (uintptr_t)out) & 15) == 0, "obs / out not 16-byte aligned");   // (first: a refusal touches nothing)
   COMMON(h, n);
   NEED(obs && out, "NULL obs / out");
   NEED(fmt >= 0 && fmt <= 2, "fmt");
@@ -70,6 +71,7 @@ extern "C" int brl_obs_cast(brl_handle *h, const uint8_t *obs, int64_t n, void *
 
 extern "C" int brl_obs_cast_rows(brl_handle *h, const uint8_t *obs, const int64_t *rows, int64_t m, void *out, int fmt,
                                  void *stream) {
+  NEED((((uintptr_t)obs | (uintptr_t)out) & 15) == 0 && (((uintptr_t)rows) & 7) == 0, "obs / out not 16-byte aligned (rows: 8-byte)");
   COMMON(h, m);
   NEED(obs && rows && out, "NULL obs / rows / out");
   NEED(fmt >= 0 && fmt <= 2, "fmt");

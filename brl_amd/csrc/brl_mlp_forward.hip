@@ -43,6 +43,11 @@ extern "C" int brl_mlp_forward_rows(int device, const brl_mlp_ref *net, const ui
   const int64_t H = net->hidden;
   NEED(scratch_len >= m * (BRL_OBS_SIZE + 2 * H) && (((uintptr_t)scratch) & 15) == 0, "scratch: m * (480 + 2 * hidden) floats, 16-byte aligned");
   NEED((((uintptr_t)net->actor_w | (uintptr_t)net->critic_w) & 15) == 0, "head weights not 16-byte aligned");
+  // the layers are brl_mlp_gemm's operands: refused HERE, before the cast launch, not by the product behind it
+  for (int l = 0; l < net->nlayers; l++)
+    NEED((((uintptr_t)net->w[l] | (uintptr_t)net->b[l]) & 15) == 0, "w[l] / b[l] not 16-byte aligned");
+  NEED((((uintptr_t)obs | (uintptr_t)net->actor_b | (uintptr_t)net->critic_b | (uintptr_t)out) & 3) == 0 && (((uintptr_t)rows) & 7) == 0,
+       "obs / actor_b / critic_b / out not 4-byte aligned (rows: 8-byte)");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   float *x = scratch, *act[2] = {scratch + m * BRL_OBS_SIZE, scratch + m * BRL_OBS_SIZE + m * H};

@@ -22,6 +22,9 @@ __global__ __launch_bounds__(mg::THREADS) void k_gemm64_dh_heads_dw(mg::Args G, 
 // Tile width of a launch: 64 x 64 tiles (one workgroup per CU at 1024 x 1024) or 64 x 32 (two per CU, and twice the tiles for
 // the step's narrow products: dW_0 is 1024 x 480 = 128 tiles of 64 x 64 on a 256-CU chip).  BRL_GEMM_TILE_N = 32 / 64 forces one
 // (A/B runs); default: 64 x 32 up to one 64 x 64 tile per CU.
+// The tile code moves 16-byte pieces (buffer_load_b128 of a / b, f32x4 loads of bias / gate, f32x4 stores of c): include/brl_hip.h.
+static inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+
 static int tile_nb(int64_t m, int64_t n) {
   static const int forced = [] {
     const char *e = getenv("BRL_GEMM_TILE_N");
@@ -48,6 +51,10 @@ extern "C" int brl_mlp_gemm(int device, int layout, int epilogue, const float *a
   // every byte offset inside an operand is a 32-bit buffer offset
   NEED((akc ? m * lda : k * lda) < (1ll << 29) && (bkc ? n * ldb : k * ldb) < (1ll << 29), "operands below 2 GB");
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
+  NEED(aligned16(a) && aligned16(b) && aligned16(c), "a / b / c not 16-byte aligned");
+  NEED((epilogue != BRL_GEMM_EPI_BIAS_ACT || aligned16(bias)) && (epilogue != BRL_GEMM_EPI_GATE_COLSUM || aligned16(gate)),
+       "bias / gate not 16-byte aligned");
+  NEED(((((uintptr_t)colsum) | ((uintptr_t)sqsum)) & 3) == 0, "colsum / sqsum not 4-byte aligned");
   NEED((epilogue == BRL_GEMM_EPI_NONE) || (epilogue == BRL_GEMM_EPI_BIAS_ACT && layout == BRL_GEMM_NT && bias) ||
            (epilogue == BRL_GEMM_EPI_GATE_COLSUM && layout == BRL_GEMM_NN && gate && ldg >= n && ldg % 4 == 0) ||
            (epilogue == BRL_GEMM_EPI_SQSUM && layout == BRL_GEMM_TN && sqsum),
@@ -93,6 +100,7 @@ extern "C" int brl_mlp_gemm_group(int device, int layout, int count, const float
   const int nb = (tiles64 <= 256) ? 1 : 2;     // (brl_mlp_gemm's rule: 64 x 32 tiles up to one 64 x 64 tile per CU)
   for (int i = 0; i < count; i++) {
     NEED(a[i] && b[i] && c[i] && m[i] > 0 && n[i] > 0 && k[i] > 0, "a / b / c / m / n / k");
+    NEED(aligned16(a[i]) && aligned16(b[i]) && aligned16(c[i]), "a / b / c not 16-byte aligned");
     NEED(m[i] < (1 << 24) && n[i] < (1 << 24) && k[i] < (1 << 24), "m / n / k below 2^24");
     NEED(n[i] % 4 == 0 && ldc[i] % 4 == 0 && lda[i] % 4 == 0 && ldb[i] % 4 == 0 && ldc[i] >= n[i], "n and the leading dimensions multiples of 4");
     NEED(!akc || k[i] % 4 == 0, "k a multiple of 4 where it is the contiguous index of an operand");
@@ -132,6 +140,8 @@ extern "C" int brl_mlp_gemm_dh_heads_dw(int device, const float *dz, int64_t ldd
   NEED(lddz >= k && ldw >= n && ldo >= n && ldg >= n, "leading dimensions");
   NEED(m * lddz < (1ll << 29) && k * ldw < (1ll << 29), "operands below 2 GB");
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
+  NEED(aligned16(dz) && aligned16(w) && aligned16(out) && aligned16(gate) && (((uintptr_t)colsum) & 3) == 0,
+       "dz / w / out / gate not 16-byte aligned (colsum: 4-byte)");
   NEED(batch > 0 && hidden > 0 && hidden % 256 == 0 && ldh >= hidden && ldh % 4 == 0, "batch / hidden (a multiple of 256) / ldh");
   NEED(dheads && h && dw_partials && db_partials, "NULL array");
   NEED(nsplit >= 1 && (batch + nsplit - 1) / nsplit <= 64, "nsplit: at most 64 rows per split");

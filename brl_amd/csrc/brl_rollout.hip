@@ -1193,6 +1193,11 @@ static int policy_step_impl(brl_handle *h, const uint64_t *state_in, uint64_t *s
                             int autoreset,
                             int32_t *action, float *log_prob, uint8_t *obs, uint8_t *mask, float *rewards_acc,
                             uint8_t *terminated_acc, int32_t *current_player, void *stream, const brl_macro_ext *ext = nullptr) {
+  NEED(step_outputs_aligned(state_in, state_out, obs, rewards_acc, action, current_player) && ptr_aligned(log_prob, 4) &&
+           ptr_aligned(draw_dev, 4), STEP_ALIGN_MSG);
+  NEED(ext == nullptr || (ptr_aligned(ext->obs_cast, 16) && ptr_aligned(ext->value_out, 4) && ptr_aligned(ext->reward_out, 4) &&
+                          ptr_aligned(ext->actor, 4) && ptr_aligned(ext->terminated_count, 8)),
+       "ext: obs_cast not 16-byte aligned (value_out / reward_out / actor: 4-byte, terminated_count: 8-byte)");
   COMMON(h, n);
   const bool heads = ext != nullptr && (ext->head_h != nullptr || ext->head_part != nullptr);
   NEED(state_in && state_out && (logits || heads), "NULL state / logits");

@@ -39,6 +39,17 @@ static inline unsigned thread_grid(int64_t n, int bs) { return (unsigned)((n + b
     HIP_TRY(hipGetLastError());                                                                              \
   } while (0)
 
+// What the per-step kernels' stores ask of the caller's arrays beyond their element types (include/brl_hip.h, brl_step): an
+// observation row leaves as 8-byte pieces per lane (emit_obs_row), a table's four rewards as ONE 16-byte store (wave_step_outputs).
+// Checked in front of COMMON: a refusal touches neither the handle nor the runtime.
+static inline bool ptr_aligned(const void *p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
+static inline bool step_outputs_aligned(const void *state_in, const void *state_out, const void *obs, const void *rewards,
+                                        const void *i32a, const void *i32b) {
+  return ptr_aligned(state_in, 8) && ptr_aligned(state_out, 8) && ptr_aligned(obs, 8) && ptr_aligned(rewards, 16) &&
+         ptr_aligned(i32a, 4) && ptr_aligned(i32b, 4);
+}
+#define STEP_ALIGN_MSG "state / obs not 8-byte aligned, rewards not 16-byte, int32 / float columns not 4-byte"
+
 #define COMMON(h, n)                 \
   NEED((h) != nullptr, "handle");    \
   NEED((n) >= 0, "n");               \

@@ -98,13 +98,17 @@ int brl_init_from_deals(brl_handle *h, uint64_t *state, int64_t n, const int32_t
  * auto_reset(env.step, env.init) — src/utils.py:9-58.  action int32 [n].
  * Optional outputs for the NEW state (any may be NULL): obs uint8 [n,480] and
  * mask uint8 [n,38] of the new current player, rewards float [n,4] by player id,
- * terminated uint8 [n], current_player int32 [n]. */
+ * terminated uint8 [n], current_player int32 [n].
+ * Alignment (here, in brl_observe and in brl_policy_step / _at / _ex; the entry points that say "as brl_step" store the same way):
+ * obs 8-byte aligned (a row leaves as 8-byte pieces), rewards / rewards_acc 16-byte (a table's four floats are ONE store),
+ * every other array as its element type (state 8, int32 / float 4, mask / terminated 1); BRL_E_ARG otherwise, before anything
+ * is launched. */
 int brl_step(brl_handle *h, const uint64_t *state_in, uint64_t *state_out, int64_t n,
              const int32_t *action, int autoreset, uint8_t *obs, uint8_t *mask, float *rewards,
              uint8_t *terminated, int32_t *current_player, void *stream);
 
 /* _observe(state, player_id) — src/duplicate.py:6,134; player_id int32 [n] or NULL for
- * state.current_player.  obs uint8 [n,480]; mask uint8 [n,38] = state.legal_action_mask
+ * state.current_player.  obs uint8 [n,480] (8-byte aligned, as brl_step's); mask uint8 [n,38] = state.legal_action_mask
  * (either may be NULL). */
 int brl_observe(brl_handle *h, const uint64_t *state, int64_t n, const int32_t *player_id,
                 uint8_t *obs, uint8_t *mask, void *stream);
@@ -211,7 +215,8 @@ typedef struct brl_macro_ext {
   float reward_scale;
   int32_t obs_fmt;           /* obs_cast element type: 0 float, 1 bf16, 2 fp16 */
   int64_t *terminated_count; /* (last) [1] += sum_i terminated_acc[i]                           (src/roll_out.py:85) */
-  void *obs_cast;            /* [n,480]: the new observation as the next forward's input (`astype`, src/roll_out.py:75) */
+  void *obs_cast;            /* [n,480]: the new observation as the next forward's input (`astype`, src/roll_out.py:75); 16-byte
+                                aligned (16-byte pieces), BRL_E_ARG otherwise */
   int32_t in_fmt;            /* element type of `logits` AND value_in as the GEMM wrote them: 0 float, 1 bf16, 2 fp16 (with 1 / 2
                                 the `logits` argument points at 2-byte elements; strides stay in elements) */
   int32_t reserved;
@@ -242,7 +247,8 @@ int brl_policy_step_ex(brl_handle *h, const uint64_t *state_in, uint64_t *state_
                        const brl_macro_ext *ext, void *stream);
 
 /* Observation bytes -> network input: `last_obs.astype(jnp.float32)` (src/roll_out.py:75) and its low-precision
- * variants.  obs uint8 [n,480] (0/1); out [n,480] of float (fmt 0), bf16 (fmt 1) or fp16 (fmt 2). */
+ * variants.  obs uint8 [n,480] (0/1); out [n,480] of float (fmt 0), bf16 (fmt 1) or fp16 (fmt 2).  obs and out 16-byte aligned
+ * (16 observation bytes in, 16-byte pieces out; rows of brl_obs_cast_rows 8-byte); BRL_E_ARG otherwise. */
 int brl_obs_cast(brl_handle *h, const uint8_t *obs, int64_t n, void *out, int fmt, void *stream);
 /* The same for the rows `rows[0..m)` of obs only: out [m,480], out row r = obs row rows[r] (an evaluator forwards the boards
  * that are still playing). */
@@ -565,7 +571,10 @@ int brl_adam_shard_apply(int device, float *p, const float *g, float *m, float *
  *                                   (clip_by_global_norm's partial sums, ppo.py:195-211)
  * n, lda, ldb, ldc (ldg) multiples of 4; k a multiple of 4 where it is an operand's contiguous index; where m is (TN), lda >= m
  * rounded up to 4 (whole 16-byte pieces are read; rows of c beyond m are not written); operands
- * below 2 GB.  Deterministic (no atomics).  Replaces torch.mm / torch.addmm + brl_act_bwd_colsum in FusedMinibatch. */
+ * below 2 GB.  Alignment: a, b, c, bias and gate 16-byte aligned (operands are fetched, bias / gate read and c stored as whole 16-byte
+ * pieces; with the multiple-of-4 leading dimensions every row then starts on one), colsum and sqsum 4-byte (one float per store);
+ * BRL_E_ARG otherwise, also for every a[i] / b[i] / c[i] of brl_mlp_gemm_group and for dz / w / out / gate of
+ * brl_mlp_gemm_dh_heads_dw.  Deterministic (no atomics).  Replaces torch.mm / torch.addmm + brl_act_bwd_colsum in FusedMinibatch. */
 #define BRL_GEMM_NT 0
 #define BRL_GEMM_NN 1
 #define BRL_GEMM_TN 2
@@ -603,7 +612,8 @@ int brl_mlp_gemm_x3_group(int device, int layout, int count, const float *const 
  * are constant over 128 forwards and an activation is split once by the launch that produces it, so the product itself is DMA -> LDS ->
  * MFMA with no vector work (brl_mlp_gemm_x3 splits every operand element once per tile that reads it).
  * brl_split_planes: x[n] (fp32, n a multiple of 4) -> planes[3][..]: plane p (0 hi, 1 mid, 2 lo; x == hi + mid + lo exactly) at
- * planes + p * plane_stride (uint16 elements). */
+ * planes + p * plane_stride (uint16 elements; plane_stride a multiple of 4).  x 16-byte aligned, planes 8-byte (four elements per
+ * load and per store); BRL_E_ARG otherwise. */
 int brl_split_planes(int device, const float *x, int64_t n, uint16_t *planes, int64_t plane_stride, void *stream);
 /* y[m, n] = (relu ? max(., 0) : .)(x[m, k] w[n, k]^T + bias[n]) — one `hk.Linear` (+ `jax.nn.relu`) of `forward_fn` (src/models.py:23-33) in
  * fp32-grade arithmetic: x as npx planes [npx][m][ldx] (plane stride sx; npx = 3, or 1 where x is exact in bf16: the 0/1 observation as the
@@ -637,7 +647,9 @@ int brl_mlp_gemm_dh_heads_dw(int device, const float *dz, int64_t lddz, const fl
  * in nn.Linear's own [out, in] layout — nothing is transposed, copied or cached), one launch for the 38 + 1 heads that writes
  * row r's logits and value to out[rows[r] * ldo + 0..38] (the scatter back included).  One host call instead of the ~8 launches
  * through torch of the library path: an evaluator's small-batch iterations are bound by host launches.
- * scratch: m * (480 + 2 * hidden) floats, 16-byte aligned.  in_features must be 480, hidden % 4 == 0 and <= 1024. */
+ * scratch: m * (480 + 2 * hidden) floats, 16-byte aligned; so are every w[l] and b[l] (brl_mlp_gemm's operands) and actor_w /
+ * critic_w (whole 16-byte pieces of a weight row); obs 4-byte, rows 8-byte, actor_b / critic_b / out 4-byte.  in_features must be
+ * 480, hidden % 4 == 0 and <= 1024. */
 typedef struct brl_mlp_ref {
   int32_t nlayers;          /* hidden layers, 1..8 */
   int32_t act;              /* 0 = ReLU, 1 = tanh (src/models.py:16) */

@@ -34,7 +34,8 @@ int brl_sl_sample(int device, const int64_t *counter, const int64_t *offsets, in
 
 /* The examples of explicit (trajectory, call index) pairs: the table dealt from hands[traj] (dealer seat 0, nobody
  * vulnerable), calls[0 .. pos) of that trajectory applied, then obs float [batch, 480] (0.0 / 1.0) of the seat to act,
- * mask uint8 [batch, 38] its legal calls and label int32 [batch] the call it made.  traj / pos out of range are clamped
+ * mask uint8 [batch, 38] its legal calls and label int32 [batch] the call it made.  obs 16-byte aligned (a row leaves as 16-byte
+ * pieces; BRL_E_ARG otherwise), every other array as its element type.  traj / pos out of range are clamped
  * into the set (a pair must name a decision point: 0 <= pos < n_calls). */
 int brl_sl_replay(int device, const uint64_t *hands, const int64_t *offsets, const uint8_t *calls, int64_t n_traj,
                   const int64_t *traj, const int32_t *pos, int64_t batch, float *obs, uint8_t *mask, int32_t *label,

@@ -76,6 +76,37 @@ def make_env(dds, k, ws=None, lut=None, **kwargs):
                 os.environ[key] = v
 
 
+def gemm_operands(layout, M, N, K, seed, device="cuda"):
+    """the operands of one brl_mlp_gemm product, uniform in [-1, 1): A ([M, K], or [K, M] for BRL_GEMM_TN), B ([N, K] for
+    BRL_GEMM_NT, else [K, N]), bias [N], gate [M, N] — drawn on `device` in that order from a generator seeded with `seed`"""
+    g = torch.Generator(device=device).manual_seed(seed)
+    r = lambda *sh: (torch.rand(sh, device=device, generator=g) * 2 - 1)  # noqa: E731
+    akc, bkc = layout != 2, layout == 0
+    A = r(M, K) if akc else r(K, M)
+    Bm = r(N, K) if bkc else r(K, N)
+    bias, gate = r(N), r(M, N)
+    return A, Bm, bias, gate
+
+
+def gemm_ref64(layout, epi, act, A, Bm, bias, gate):
+    """the float64 product of those operands with brl_mlp_gemm's epilogue `epi` (1: bias + ReLU / tanh, 2: the activation
+    derivative from `gate`; 0 and 3 leave the product as it is)"""
+    a64 = A.double() if layout != 2 else A.double().t()
+    b64 = Bm.double().t() if layout == 0 else Bm.double()
+    ref = a64 @ b64
+    if epi == 1:
+        ref = ref + bias.double()
+        ref = ref.clamp_min(0) if act == 0 else ref.tanh()
+    if epi == 2:
+        ref = ref * ((gate > 0).double() if act == 0 else (1 - gate.double() ** 2))
+    return ref
+
+
+def gemm_bound(ref, K):
+    """max |brl_mlp_gemm - float64| allowed: fp32 k-ordered fma chains, 2e-4 * max|ref| at K = 1024"""
+    return 2e-4 * max(1.0, float(ref.abs().max())) * (K / 1024 + 1) ** 0.5
+
+
 def replay_policy_rollout(oracle, ref, traj, sub_actions, seed, reward_scale=7600.0, env_offset=0, detail=None):
     """Replays the recorded actions of a policy-in-the-loop rollout (sub-step 1: traj.action, sub-steps 2-4:
     sub_actions) through the oracle's auto_reset(step) and returns the Transition columns the reference's _env_step

@@ -1,0 +1,267 @@
+"""Guarded arrays for the memory-contract tests (DESIGN.md "Memory contract"): the part of a sanitizer's job that can be done
+inside memory the process owns.
+
+An ``Arena`` is ONE uint8 tensor.  Every array of a launch — inputs and outputs — is ``place``d inside it:
+  * at EXACTLY the alignment asked for (``addr % (2 * align) == align``): a kernel that assumes more than its header states
+    reads or writes the wrong bytes;
+  * with the row pitch / strides asked for, so a leading dimension can be larger than dense;
+  * with at least ``GUARD`` bytes of arena in front of and behind it, so a small overrun or a whole-piece over-read stays inside
+    the allocation: nothing here depends on a fault.
+Every byte that is not a logical element of a placed array is a GUARD byte: the gaps, and the padding columns between rows.
+Guard bytes carry a position-dependent pattern (a kernel that stores the pattern's byte somewhere else is still seen); in the
+padding of INPUT arrays they are 0xFF — NaN in fp32, bf16 and fp16 — so padding that is read into arithmetic poisons the result.
+The logical elements of an OUTPUT start as a NaN / negative-integer variant of the pattern that no kernel result equals, so
+``unwritten`` tells which elements a launch never stored.  ``check`` compares every guard byte with a host mirror and names the
+nearest array, row, column and byte offset of the first difference.
+
+Also here: the ledger of which C-ABI entry points run under these guards (``COVERED``) and which do not yet (``OPEN``);
+tests/test_guarded_host.py holds every ``int brl_*(`` declaration of include/*.h against the two.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+GUARD = 4096          # bytes of arena in front of and behind every placed array
+_BASE_ALIGN = 512     # the arena's own base: every alignment up to 256 can be hit exactly
+
+
+def pattern(lo: int, hi: int) -> np.ndarray:
+    """the guard byte of arena offsets [lo, hi): position-dependent, never 0x00 (a stray zero store is seen everywhere)"""
+    i = np.arange(lo, hi, dtype=np.int64)
+    b = ((i * 37) ^ (i >> 8) * 101 ^ 0x5B) & 0xFF
+    return np.where(b == 0, 0xA7, b).astype(np.uint8)
+
+
+class GuardError(AssertionError):
+    pass
+
+
+class _Rec:
+    __slots__ = ("name", "off", "shape", "strides", "itemsize", "dtype", "output", "extent", "view")
+
+
+class Arena:
+    def __init__(self, device="cpu", capacity=1 << 22):
+        self.capacity = int(capacity)
+        self._raw = torch.empty(self.capacity + _BASE_ALIGN, dtype=torch.uint8, device=device)
+        skew = (-self._raw.data_ptr()) % _BASE_ALIGN
+        self.buf = self._raw[skew:skew + self.capacity]
+        self.base = self.buf.data_ptr()
+        assert self.base % _BASE_ALIGN == 0
+        self.expected = pattern(0, self.capacity)          # host mirror of every byte as placed
+        self.logical = np.zeros(self.capacity, dtype=bool)  # bytes that belong to a logical element of a placed array
+        self.readonly = np.zeros(self.capacity, dtype=bool)  # ... of an INPUT that no launch may change: checked like guard bytes
+        self.buf.copy_(torch.from_numpy(self.expected))
+        self.recs: list[_Rec] = []
+        self._cursor = 0
+
+    # ---- placing -------------------------------------------------------------------------------------------------------
+    def place(self, shape, dtype, align, ld=None, fill=None, strides=None, name=None, inout=False):
+        """A view of `shape` / `dtype` inside the arena whose address is `align`-byte aligned and NOT 2 * align aligned.
+        ld: row pitch in elements (default dense); strides: all element strides (outer dimensions further apart than dense:
+        plane strides, part strides).  fill: the values of an INPUT (anything torch.as_tensor takes; its padding becomes 0xFF);
+        None: an OUTPUT (logical elements = the unwritten fill, padding = the position pattern).  An input's elements must still
+        hold their values at `check` — unless it is `inout` (a state updated in place, a counter, a workspace)."""
+        shape = tuple(int(s) for s in ((shape,) if isinstance(shape, int) else shape))
+        assert len(shape) >= 1 and all(s > 0 for s in shape)
+        itemsize = torch.empty((), dtype=dtype).element_size()
+        assert align >= itemsize and align % itemsize == 0 and align & (align - 1) == 0 and 2 * align <= _BASE_ALIGN, align
+        if strides is None:
+            st = [1] * len(shape)
+            for d in range(len(shape) - 2, -1, -1):
+                st[d] = st[d + 1] * shape[d + 1]
+                if d == len(shape) - 2 and ld is not None:
+                    assert ld >= shape[-1]
+                    st[d] = int(ld)
+            strides = tuple(st)
+        strides = tuple(int(s) for s in strides)
+        assert len(strides) == len(shape) and strides[-1] == 1
+        for d in range(len(shape) - 1):
+            assert strides[d] >= strides[d + 1] * shape[d + 1], "strides must not overlap"
+        extent = (shape[0] * strides[0] if len(shape) > 1 else shape[0]) * itemsize   # whole pitches: the last row's padding too
+        off = self._cursor + GUARD
+        off += (align - (self.base + off)) % (2 * align)
+        assert (self.base + off) % (2 * align) == align
+        assert off + extent + GUARD <= self.capacity, f"arena too small: {off + extent + GUARD} > {self.capacity}"
+        self._cursor = off + extent
+
+        r = _Rec()
+        r.name, r.off, r.shape, r.strides, r.itemsize, r.dtype = name or f"array{len(self.recs)}", off, shape, strides, itemsize, dtype
+        r.output, r.extent = fill is None, extent
+        idx = self._byte_index(r)                       # [numel, itemsize] arena offsets of the logical elements' bytes
+        if fill is None:
+            b = self.expected[idx].copy()
+            b[:, -1] = 0xFF                             # little-endian: the most significant byte
+            if itemsize >= 2:
+                b[:, -2] |= 0xC0                        # fp32 / bf16 / fp16: a NaN; integers: large and negative
+            self.expected[idx] = b
+        else:
+            self.expected[off:off + extent] = 0xFF
+            v = torch.empty(idx.shape[0], dtype=dtype)      # (a fresh dense copy: a one-element expand keeps stride 0)
+            v.copy_(torch.as_tensor(fill).detach().to("cpu").to(dtype).expand(shape).reshape(-1))
+            self.expected[idx] = v.view(torch.uint8).numpy().reshape(-1, itemsize)
+        self.logical[idx] = True
+        if fill is not None and not inout:
+            self.readonly[idx] = True
+        self.buf[off:off + extent].copy_(torch.from_numpy(self.expected[off:off + extent]))
+        typed = self.buf[off:off + extent].view(dtype)
+        r.view = torch.as_strided(typed, shape, strides)
+        assert r.view.data_ptr() == self.base + off
+        self.recs.append(r)
+        return r.view
+
+    @staticmethod
+    def _elem_offsets(shape, strides):
+        o = np.zeros((), dtype=np.int64)
+        for n, s in zip(shape, strides):
+            o = o[..., None] + np.arange(n, dtype=np.int64) * s
+        return o
+
+    def _byte_index(self, r, sel=None):
+        e = self._elem_offsets(r.shape, r.strides)
+        if sel is not None:
+            e = e[sel]
+        return r.off + e.reshape(-1, 1) * r.itemsize + np.arange(r.itemsize, dtype=np.int64)
+
+    def rec(self, view) -> _Rec:
+        p = view if isinstance(view, int) else view.data_ptr()
+        for r in self.recs:
+            if self.base + r.off == p:
+                return r
+        raise KeyError("not a placed array of this arena")
+
+    # ---- checking ------------------------------------------------------------------------------------------------------
+    def snapshot(self) -> np.ndarray:
+        if self.buf.is_cuda:
+            torch.cuda.synchronize(self.buf.device)
+        return self.buf.cpu().numpy()
+
+    def unwritten(self, view, cur=None) -> np.ndarray:
+        """bool array of the view's logical shape: True where an element still holds the bytes it was placed with"""
+        r = self.rec(view)
+        cur = self.snapshot() if cur is None else cur
+        idx = self._byte_index(r)
+        return (cur[idx] == self.expected[idx]).all(axis=1).reshape(r.shape)
+
+    def describe(self, i: int) -> str:
+        """the placed array nearest to arena offset i, and where i lies relative to it"""
+        def dist(r):
+            return 0 if r.off <= i < r.off + r.extent else (r.off - i if i < r.off else i - (r.off + r.extent) + 1)
+        r = min(self.recs, key=dist)
+        rel = i - r.off
+        if rel < 0:
+            return f"{-rel} byte(s) BEFORE array '{r.name}' (byte offset {rel})"
+        if rel >= r.extent:
+            return f"{rel - r.extent + 1} byte(s) BEHIND array '{r.name}' (byte offset {rel} from its start, extent {r.extent})"
+        e, pos = rel // r.itemsize, []
+        for s in r.strides:
+            pos.append(e // s)
+            e -= pos[-1] * s
+        outer = "".join(f"[{p}]" for p in pos[:-2])
+        row, col = (pos[-2] if len(pos) > 1 else 0), pos[-1]
+        return (f"array '{r.name}'{outer} row {row} column {col} (width {r.shape[-1]}, pitch "
+                f"{r.strides[-2] if len(pos) > 1 else r.shape[-1]}; byte offset {rel} from its start)")
+
+    def check(self, allowed=(), cur=None):
+        """Every guard byte, and every element of an input that is not `inout`, is as placed.  allowed: (view, col_lo, col_hi) triples — columns [col_lo, col_hi) of every row of that
+        array are padding the header lets the kernel write: each 4-byte word there holds exactly 0.0f or its pattern."""
+        cur = self.snapshot() if cur is None else cur
+        bad = (cur != self.expected) & (~self.logical | self.readonly)
+        for view, lo, hi in allowed:
+            r = self.rec(view)
+            assert r.itemsize == 4 and r.shape[-1] <= lo <= hi <= r.strides[-2]
+            if hi == lo:
+                continue
+            e = self._elem_offsets(r.shape[:-1], r.strides[:-1])[..., None] + np.arange(lo, hi, dtype=np.int64)
+            idx = r.off + e.reshape(-1, 1) * 4 + np.arange(4, dtype=np.int64)
+            ok = (cur[idx] == self.expected[idx]).all(axis=1) | (cur[idx] == 0).all(axis=1)
+            bad[idx[ok]] = False
+        if bad.any():
+            i = int(np.argmax(bad))
+            what = "input element" if self.readonly[i] else "guard byte"
+            raise GuardError(f"{what} changed at arena offset {i}: {self.describe(i)}; placed 0x{self.expected[i]:02x}, "
+                             f"found 0x{cur[i]:02x}; {int(bad.sum())} guarded byte(s) differ in all")
+        return cur
+
+    def assert_written(self, *views, cur=None):
+        cur = self.snapshot() if cur is None else cur
+        for v in views:
+            u = self.unwritten(v, cur)
+            if u.any():
+                first = tuple(int(x) for x in np.argwhere(u)[0])
+                raise GuardError(f"array '{self.rec(v).name}': {int(u.sum())} of {u.size} elements were never written, first {first}")
+
+
+def round_up(x: int, q: int) -> int:
+    return (x + q - 1) // q * q
+
+
+# ---- the ledger: every `int brl_*(` of include/*.h is in exactly one of the two ------------------------------------------------
+# COVERED: entry point -> what tests/test_gpu_memory_contract.py runs it on (alignments, strides, shapes)
+COVERED = {
+    "brl_mlp_gemm": "a / b / c / bias / gate at 16 bytes, colsum / sqsum at 4 and exactly sized; lda / ldb / ldc / ldg = dense + 4; NT, NN, TN x "
+                    "every epilogue at (4,4,4), (68,36,52), (60,132,8); 64 x 32 tiles, and 64 x 64 in a child process (BRL_GEMM_TILE_N=64)",
+    "brl_mlp_gemm_group": "the same three shapes + (TN) the 39-of-40 head product in one launch; 16 bytes, every ld + 4; 64 x 32 tiles only "
+                          "(the 64 x 64 ones need > 256 tiles in one launch)",
+    "brl_mlp_gemm_x3": "16 bytes (colsum too), ld + 4, (4,4,32), (132,132,160), (68,260,128), every layout and epilogue, without and with the "
+                       "workspace (at 256 bytes, exactly *bytes long; tickets zero afterwards)",
+    "brl_mlp_gemm_x3_workspace": "host only: its *bytes size the guarded workspace of brl_mlp_gemm_x3",
+    "brl_mlp_gemm_x3_group": "the three x3 shapes in one launch per layout; 16 bytes, ld + 4",
+    "brl_split_planes": "x at 16, planes at 8; n in {4, 36}; plane_stride = n + 8",
+    "brl_linear_x3p": "16 bytes; m in {1, 129}, n = 128, k in {32, 96}, npx in {1, 3}; ldx / ldw / ldy / ldyp + 8, plane strides + 8; "
+                      "y only, planes only, both",
+    "brl_linear_act": "bf16 / fp16, 16 bytes, m in {1, 65}, n_out in {128, 256}, k in {8, 480}, ldx / ldw / ldy + 8, NaN beyond column k",
+    "brl_linear_act_heads": "as brl_linear_act; ld_head_w + 8, head_part_ld in {40, 44}, head_part_stride + 4, y given and NULL; the columns "
+                            "[39, 40) of head_part may hold 0.0",
+    "brl_obs_cast": "n in {1, 3, 33}, three formats; obs and out at 16",
+    "brl_obs_cast_rows": "every other row of n in {1, 3, 33}, three formats; obs and out at 16, rows at 8",
+    "brl_live_index": "n in {1, 3, 33}; terminated at 1 and at 8 (its two load paths), live / finished at 8; entries behind n - finished untouched; "
+                      "live = NULL",
+    "brl_gae": "n in {1, 3, 33, 65} x T in {1, 7}; floats at 4, done at 1",
+    "brl_init_random": "n in {1, 3, 33, 65}; state at 8",
+    "brl_step": "n in {1, 3, 33, 65}; state at 8, obs at 8, mask / terminated at 1, rewards at 16, int32 columns at 4; every optional output "
+                "given, and every one NULL",
+    "brl_observe": "n in {1, 3, 33, 65}; player_id given and NULL; obs only, mask only, both",
+    "brl_policy_step_ex": "n in {1, 3, 33}; state and obs at 8, rewards_acc at 16; logits_stride 39 / 40 (value_in at that stride, NaN in column 39), obs_cast in each format at 16, "
+                          "done_out / reward_out / value_out / terminated_count; every optional output given, and every one NULL",
+    "brl_rollout_random": "(n, T) in {(1,1), (33,5), (96,9)}, substeps 1 and 4, the default kernels and the K-tables-per-wave one; every "
+                          "Transition column its own placement, done at 4, everything else at 16",
+    "brl_rollout_random_gae": "the same shapes: one launch at (96,9), rollout + scan at the others; advantages / targets at 16, last_val at 4",
+    "brl_mlp_forward_rows": "hidden in {64, 260}, nlayers in {1, 3}, 5 rows out of 9, ldo in {40, 44}; weights / hidden biases / scratch at 16, "
+                            "head biases and obs at 4, rows at 8; scratch exactly m (480 + 2 hidden) floats",
+    "brl_sl_sample": "batch in {1, 5, 257}; int64 at 8, pos at 4",
+    "brl_sl_replay": "batch in {1, 5, 257}; obs at 16, mask at 1, label at 4",
+    "brl_sl_loss": "batch in {1, 5, 257}; logits stride 40 with NaN padding; dlogits given and NULL; counter given and NULL",
+    "brl_distill_targets": "B in {1, 65}, K = 2; rows of 40 floats (NaN padding, teachers 4 floats further apart than dense) and the [K, n, 39] "
+                           "heads; floats at 4, mask at 1",
+    "brl_distill_loss": "as brl_distill_targets; u at stride 2; work at 8, exactly 8 doubles per block of 64 rows; dz / du given and NULL",
+}
+
+_NOT_YET = "not yet placed in an arena: "
+# OPEN: entry point -> why it does not run under the guards (yet)
+OPEN = {
+    # host-only or no device arrays of the caller's
+    "brl_version": "no pointer arguments",
+    "brl_create": "host pointers only (the LUT is copied into memory the library owns)",
+    "brl_set_lut": "host pointers only",
+    "brl_destroy": "no arrays",
+    "brl_set_rng": "no arrays",
+}
+for _n, _why in {
+    "brl_mlp_gemm_dh_heads_dw": "brl_mlp_gemm's tile code (guarded there) + the heads' dW role, which needs the step's 256-multiple hidden sizes",
+    "brl_policy_step": "brl_policy_step_ex with dense logits and no ext block (the same kernel, guarded there)",
+    "brl_policy_step_at": "brl_policy_step_ex without the ext block (the same kernel, guarded there)",
+    "brl_init_from_deals": "", "brl_get_fields": "", "brl_imp_reward": "", "brl_duplicate_step": "",
+    "brl_eval_step": "", "brl_eval_step_team": "", "brl_eval_reduce": "",
+    "brl_ppo_loss": "", "brl_ppo_stats": "", "brl_ppo_heads_loss_split": "", "brl_ppo_heads_bwd": "", "brl_ppo_stats_gram": "",
+    "brl_ppo_illegal_grad": "", "brl_ppo_stats_rows": "", "brl_mb_gather_bind": "", "brl_mb_gather_dev": "",
+    "brl_act_bwd_colsum": "", "brl_act_bwd_colsum_heads_dw": "", "brl_bias_finalize_ex": "", "brl_bias_finalize_rows": "",
+    "brl_fair_forward": "", "brl_fair_chain": "", "brl_adam_clip_fin_gather": "", "brl_adam_shard_norm": "", "brl_adam_shard_apply": "",
+    "brl_league_route": "", "brl_league_forward": "", "brl_board_records": "", "brl_board_imp": "", "brl_board_keep_a": "",
+    "brl_book_samples": "", "brl_book_reduce": "", "brl_par": "", "brl_par_imp": "", "brl_review_expand": "", "brl_review_reduce": "",
+    "brl_belief_deal": "", "brl_belief_logp": "", "brl_belief_reduce": "", "brl_belief_resample": "", "brl_belief_propose": "",
+    "brl_belief_accept": "", "brl_compare_tables": "", "brl_compare_rows": "", "brl_compare_reduce": "", "brl_xplay_route": "",
+    "brl_lines_init": "", "brl_lines_expand": "", "brl_lines_finish": "", "brl_lines_imp": "",
+}.items():
+    OPEN[_n] = _NOT_YET + (_why or "compared with its reference on dense torch tensors only")

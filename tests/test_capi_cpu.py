@@ -110,6 +110,80 @@ def test_bad_arguments_are_reported_not_crashed(built_lib):
     assert L.brl_destroy(None) == 0
 
 
+def test_fp32_gemm_entry_points_refuse_misaligned_pointers(built_lib):
+    """include/brl_hip.h: a / b / c / bias / gate of brl_mlp_gemm, brl_mlp_gemm_group and brl_mlp_gemm_dh_heads_dw 16-byte
+    aligned (the tile code moves 16-byte pieces), colsum / sqsum 4-byte.  The argument checks come before anything touches a
+    device, so a refusal needs none: the addresses here are made up, nothing reads them and nothing is launched."""
+    from brl_amd import _capi
+    L = _capi.lib()
+    P = 0x7F0000000000      # "a pointer": 16-byte aligned, never dereferenced
+    DEV = 1 << 20           # no such device: were a check missing, hipSetDevice would fail (BRL_E_HIP) before any launch; a refusal
+                            # returns before the runtime is touched at all (no sticky HIP error is left for the next caller)
+
+    def gemm(layout=0, epi=0, a=P, b=P, c=P, bias=None, gate=None, colsum=None, sqsum=None):
+        return L.brl_mlp_gemm(DEV, layout, epi, a, 8, b, 8, c, 8, 8, 8, 8, 0, bias, gate, 8, colsum, sqsum, None)
+    for kw, what in ((dict(a=P + 4), b"a / b / c"), (dict(b=P + 8), b"a / b / c"), (dict(c=P + 12), b"a / b / c"),
+                     (dict(epi=1, bias=P + 4), b"bias / gate"), (dict(layout=1, epi=2, gate=P + 8), b"bias / gate"),
+                     (dict(layout=1, epi=2, gate=P, colsum=P + 2), b"colsum / sqsum"),
+                     (dict(layout=2, epi=3, sqsum=P + 1), b"colsum / sqsum")):
+        assert gemm(**kw) == -1 and what in L.brl_last_error() and b"aligned" in L.brl_last_error(), kw
+    vp, i64 = ctypes.c_void_p * 2, ctypes.c_int64 * 2
+    eight = i64(8, 8)
+    for bad in range(3):
+        ptrs = [vp(P, P + 4) if j == bad else vp(P, P) for j in range(3)]
+        assert L.brl_mlp_gemm_group(DEV, 2, 2, ptrs[0], eight, ptrs[1], eight, ptrs[2], eight, eight, eight, eight, None) == -1
+        assert b"16-byte aligned" in L.brl_last_error()
+    for bad in range(5):
+        dz, w, out, gate, colsum = [P + (2 if j == 4 else 4) if j == bad else P for j in range(5)]
+        assert L.brl_mlp_gemm_dh_heads_dw(DEV, dz, 256, w, 256, out, 256, 64, 256, 256, 0, gate, 256, colsum, P, P, 256, 64, 256, 1,
+                                          P, P, None, None, 0, None, None, None, None) == -1
+        assert b"16-byte aligned" in L.brl_last_error()
+
+
+def test_handle_entry_points_refuse_misaligned_pointers_before_anything_else(built_lib):
+    """brl_mlp_forward_rows (w[l] / b[l] at 16 bytes: brl_mlp_gemm's operands, refused before its first launch; obs at 4, rows at
+    8), brl_obs_cast / _rows (obs and out at 16, rows at 8), brl_step / brl_observe / brl_policy_step_ex (obs at 8, rewards at 16,
+    brl_macro_ext.obs_cast at 16): the alignment checks stand in front of the handle and device checks, so made-up addresses and
+    no handle are enough to ask for them — nothing is read, nothing is launched."""
+    from brl_amd import _capi
+    L = _capi.lib()
+    P, DEV = 0x7F0000000000, 1 << 20
+
+    def refused(rc, what):
+        assert rc == -1 and what in L.brl_last_error(), (rc, L.brl_last_error())
+    for field, off, what in (("w", 4, b"w[l] / b[l]"), ("b", 8, b"w[l] / b[l]"), ("obs", 2, b"obs /"), ("rows", 4, b"rows: 8-byte"),
+                             ("critic_b", 2, b"critic_b")):
+        r = _capi.MlpRef()
+        r.nlayers, r.act, r.in_features, r.hidden = 2, 0, 480, 64
+        for l in range(2):
+            r.w[l], r.b[l] = P, P
+        r.actor_w = r.actor_b = r.critic_w = r.critic_b = P
+        if field in ("w", "b"):
+            getattr(r, field)[1] = P + off          # the SECOND layer: refused before the first one is launched
+        elif field == "critic_b":
+            r.critic_b = P + off
+        obs, rows = (P + off if field == "obs" else P), (P + off if field == "rows" else P)
+        refused(L.brl_mlp_forward_rows(DEV, ctypes.byref(r), obs, rows, 1, P, 1 << 20, P, 40, None), what)
+    refused(L.brl_obs_cast(None, P + 8, 4, P, 0, None), b"obs / out not 16-byte aligned")
+    refused(L.brl_obs_cast(None, P, 4, P + 8, 0, None), b"obs / out not 16-byte aligned")
+    refused(L.brl_obs_cast_rows(None, P + 8, P, 4, P, 0, None), b"obs / out not 16-byte aligned")
+    refused(L.brl_obs_cast_rows(None, P, P + 4, 4, P, 0, None), b"rows: 8-byte")
+    step = lambda **k: L.brl_step(None, k.get("si", P), k.get("so", P), 4, k.get("act", P), 0, k.get("obs", P), P + 1,   # noqa: E731
+                                  k.get("rew", P), P + 1, k.get("cur", P), None)
+    for kw in (dict(si=P + 4), dict(so=P + 4), dict(act=P + 2), dict(obs=P + 4), dict(rew=P + 8), dict(cur=P + 2)):
+        refused(step(**kw), b"rewards not 16-byte")
+    assert step() == -1 and b"handle" in L.brl_last_error()      # aligned (mask and terminated at an odd address): on to the handle
+    refused(L.brl_observe(None, P, 4, P, P + 4, P + 1, None), b"obs not 8-byte")
+    refused(L.brl_observe(None, P + 4, 4, None, P, None, None), b"obs not 8-byte")
+    pol = lambda ext=None, **k: L.brl_policy_step_ex(None, P, P, 4, P, 38, 0, None, 0, 0, P, P, k.get("obs", P), P + 1,   # noqa: E731
+                                                     k.get("rew", P), P + 1, P, ext, None)
+    refused(pol(obs=P + 4), b"obs not 8-byte")
+    refused(pol(rew=P + 8), b"rewards not 16-byte")
+    refused(pol(ctypes.byref(_capi.MacroExt(obs_cast=P + 8))), b"obs_cast not 16-byte aligned")
+    refused(pol(ctypes.byref(_capi.MacroExt(obs_cast=P, terminated_count=P + 4))), b"terminated_count: 8-byte")
+    assert pol(ctypes.byref(_capi.MacroExt(obs_cast=P))) == -1 and b"handle" in L.brl_last_error()
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     import brl_amd

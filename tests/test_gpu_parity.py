@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from tests.conftest import synthetic_lut
-from tests.gpu_util import _assert_log_info, assert_state_equal, make_env, random_legal_actions, replay_policy_rollout, to_np
+from tests.gpu_util import (_assert_log_info, assert_state_equal, gemm_bound, gemm_operands, gemm_ref64, make_env, random_legal_actions,
+                            replay_policy_rollout, to_np)
 
 pytestmark = pytest.mark.gpu
 
@@ -2694,12 +2695,7 @@ def test_mlp_gemm_matches_float64(layout, epi, M, N, K, act):
     K = 1024 (the same class of result as the library GEMM it replaces, src/update.py:86-178)."""
     from brl_amd import _capi
     L = _capi.lib()
-    g = torch.Generator(device="cuda").manual_seed(layout * 1000 + M + N + K)
-    r = lambda *sh: (torch.rand(sh, device="cuda", generator=g) * 2 - 1)  # noqa: E731
-    akc, bkc = layout != 2, layout == 0
-    A = r(M, K) if akc else r(K, M)
-    Bm = r(N, K) if bkc else r(K, N)
-    bias, gate = r(N), r(M, N)
+    A, Bm, bias, gate = gemm_operands(layout, M, N, K, layout * 1000 + M + N + K)
     C = torch.full((M, N), float("nan"), device="cuda")
     tm, tn = (M + 63) // 64, (N + 63) // 64
     colsum = torch.full((tm, N), float("nan"), device="cuda")
@@ -2708,15 +2704,8 @@ def test_mlp_gemm_matches_float64(layout, epi, M, N, K, act):
     _capi.check(L.brl_mlp_gemm(0, layout, epi, A.data_ptr(), A.stride(0), Bm.data_ptr(), Bm.stride(0), C.data_ptr(), N, M, N, K, act,
                                bias.data_ptr(), gate.data_ptr(), N, colsum.data_ptr(), sqsum.data_ptr(), s))
     torch.cuda.synchronize()
-    a64 = A.double() if akc else A.double().t()
-    b64 = Bm.double().t() if bkc else Bm.double()
-    ref = a64 @ b64
-    if epi == 1:
-        ref = ref + bias.double()
-        ref = ref.clamp_min(0) if act == 0 else ref.tanh()
-    if epi == 2:
-        ref = ref * ((gate > 0).double() if act == 0 else (1 - gate.double() ** 2))
-    tol = 2e-4 * max(1.0, float(ref.abs().max())) * (K / 1024 + 1) ** 0.5
+    ref = gemm_ref64(layout, epi, act, A, Bm, bias, gate)
+    tol = gemm_bound(ref, K)
     assert float((C.double() - ref).abs().max()) < tol
     if epi == 2:   # column sums of what was STORED, per 64-row tile, in a fixed order: compare with the fp64 sums of C itself
         want = torch.stack([C[64 * t:64 * t + 64].double().sum(0) for t in range(tm)])
