@@ -10,6 +10,9 @@
 //     wave never waits for a follower: it posts slot s and publishes `posted = s + 1` with a plain LDS store (LDS
 //     operations of one wave are performed in order, so a reader that sees the counter sees the commands);
 //   * every follower consumes slot s as soon as it is posted, at its own pace (it polls `posted` only when it has caught up);
+//   * the emit waves do not wait for slot 0 at all: its rows show the incoming tables to their acting seats, which the
+//     incoming scalars in `img` name (nobody writes them during the launch: the final ones travel in raw[total]), so the
+//     first observation stores leave right behind the prologue's barrier, ~1.4 k cycles before `posted` reaches 1;
 //   * <= 11 boards per table can be dealt in <= 40 sub-steps, so the 12-entry board ring never wraps: the loader fetches
 //     all 12 boards of every table up front (two per pass, one in each half of the wave), publishes `ring_count`, and
 //     then turns into the wave that writes the legal-mask rows;
@@ -20,6 +23,8 @@
 //     who acted, which boards ended) and queues the finished boards; SCORER B scores them one lane per board and writes
 //     the scalar columns 8 slots at a time.  B is done ~6 k cycles after the logic wave, so the optional calc_gae scan
 //     (brl_rollout_random_gae: on the logic wave, once B has every slot's reward in LDS) ends before the emit waves do.
+// The prologue puts everything that needs no loaded value (reward rows, counters) into LDS before the first use of a
+// loaded register: those stores issue under the loads' latency instead of behind it (barrier 4.65 -> 4.35 k cycles, §13).
 // Why (profiles/r02/r02_rollout_experiments.txt §5): with the output going to HBM the launch is  T = (time until the
 // stores start and are never starved) + (store time of 140 MB).  A store-only probe paced like this hand-off
 // (scripts/micro/store_test4.hip) needs 24-25 us; paced like k_rollout_ws's batches (1,3,4,8,8,..) 29-31 us.
@@ -143,7 +148,18 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       oi_sc[k] = st32[t * 32 + 2 * W_SC];
     }
   }
-  if (tid <= BRL_NUM_ACTIONS) s_neglog[tid] = A.neg_log_n[tid];
+  const float neglog_v = (tid <= BRL_NUM_ACTIONS) ? A.neg_log_n[tid] : 0.0f;  // (stored behind the image build)
+  // What needs no loaded value goes to LDS here, under the loads' latency (~3 k cycles), not behind the wait for them
+  for (int i = tid; i < FS_MAX_TOTAL * TPB; i += NW * 64) (&frew[0][0])[i] = 0.0f;
+  if (tid < TPB * 4) (&last_rw[0][0])[tid] = 0u;
+  if (tid == 0) {
+    posted = 0;
+    raw_posted = 0;
+    ring_count = 0;
+    gae_ready = 0;
+    scored = 0;
+    ev_count = 0;
+  }
   // (loader) board pass i: lanes 0..31 fetch board nb0 + 2 i of their table, lanes 32..63 board nb0 + 2 i + 1 (Philox ->
   // LUT row -> packed hand words + DDS values, 48 B) into ring entries 2 i, 2 i + 1.  Passes 0 and 1 are ISSUED HERE, before
   // the workgroup's barrier: the logic wave needs the first two entries of every table at its first deal, a few hundred
@@ -204,16 +220,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       oimg[t][o][q] = v;
     }
   }
-  for (int i = tid; i < FS_MAX_TOTAL * TPB; i += NW * 64) (&frew[0][0])[i] = 0.0f;
-  if (tid < TPB * 4) (&last_rw[0][0])[tid] = 0u;
-  if (tid == 0) {
-    posted = 0;
-    raw_posted = 0;
-    ring_count = 0;
-    gae_ready = 0;
-    scored = 0;
-    ev_count = 0;
-  }
+  if (tid <= BRL_NUM_ACTIONS) s_neglog[tid] = neglog_v;
   FS_STAMP(11);  // images built
   __syncthreads();  // images, draws and the two counters are in LDS
   FS_STAMP(12);
@@ -241,6 +248,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       if (c.lane < TPB) *reinterpret_cast<uint4 *>(&raw[s][tl][0]) = make_uint4(sc, sch, pa, psc);
       if (c.lane == 0) fs_flag_write(&raw_posted, s + 1);
       if ((s & 7) == 0) FS_STAMP(s >> 3);
+      if (s == 1 || s == 2) FS_STAMP(12 + s);  // raw_posted = 2, 3
       if (s == total) break;
       const uint32_t u = un;
       un = udraw[(s + 2 < total) ? s + 1 : total - 1][tl];  // next sub-step's draw, off the chain
@@ -272,8 +280,9 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
       }
     }
     if (c.lane < TPB) {
+      // (the final sc, sch are raw[total]'s: the image keeps the incoming ones, which the emit waves read for slot 0 at
+      //  a time of their own)
       uint2 *p = reinterpret_cast<uint2 *>(img + tl * TABLE_BYTES);
-      p[W_SC] = make_uint2(sc, sch);
       p[W_CTR] = make_uint2(lut, bctr);
     }
     if (A.gae_adv != nullptr) {
@@ -342,6 +351,11 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
         const uint32_t w0 = cmd_pack_w0(pend, seat, 0u);  // (no vulnerability nibble: the emit waves' observer images hold it)
         *reinterpret_cast<uint4 *>(&cmd[ms][lt][0]) = make_uint4(w0, cur.w, (uint32_t)legal, cmd_pack_w3(legal, a));
       }
+#ifdef BRL_TIMING
+      if (s == 0) FS_STAMP(0);                    // posted >= 1
+      if (s < 2 && s + (two ? 2 : 1) >= 2) FS_STAMP(13);  // posted >= 2
+      if (s < 3 && s + (two ? 2 : 1) >= 3) FS_STAMP(14);  // posted >= 3
+#endif
       s += two ? 2 : 1;
       if (c.lane == 0) fs_flag_write(&posted, s);
     }
@@ -499,12 +513,27 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
     const int dl_o = active ? L / 15 : 3, dl_q = active ? L - 15 * (L / 15) : 15;  // deals: lane = (observer, dword)
     uint8_t *optr = A.out.obs + (table0 + 4 * g) * BRL_OBS_SIZE + 16 * L;
     const int64_t ostep = A.n * BRL_OBS_SIZE;
+    // Slot 0 does not wait for the logic and prep waves: its command is (no call before it, observer = the acting seat of
+    // the incoming scalars), and those scalars stand in `img`, which nobody writes while the launch runs (the logic wave
+    // leaves its final sc, sch in raw[total]).  So the first rows leave right behind the barrier, ~1.4 k cycles before
+    // `posted` reaches 1.  Every later slot waits for the prep wave, which waits for the logic wave, which waits for the
+    // loader only: none of them ever waits for an emit wave.
     int avail = 0;
     for (int s = 0; s <= total; s++) {
 #ifdef BRL_TIMING
       const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
 #endif
-      fs_wait(&posted, s, avail);
+      uint32_t w0a, w0b;
+      if (s == 0) {
+        const uint2 sa = reinterpret_cast<const uint2 *>(img + (4 * g + r) * TABLE_BYTES)[W_SC];
+        const uint2 sb = reinterpret_cast<const uint2 *>(img + (4 * g + r + 2) * TABLE_BYTES)[W_SC];
+        w0a = cmd_pack_w0(0u, lean_seat(sa.x, sa.y), 0u);
+        w0b = cmd_pack_w0(0u, lean_seat(sb.x, sb.y), 0u);
+      } else {
+        fs_wait(&posted, s, avail);
+        w0a = cmd[s][4 * g + r][0];
+        w0b = cmd[s][4 * g + r + 2][0];
+      }
 #ifdef BRL_TIMING
       t_wait += __builtin_amdgcn_s_memtime() - tw0;
       if ((s & 7) == 0) FS_STAMP(s >> 3);
@@ -516,8 +545,6 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
         if (hw_wave >= 8) __builtin_amdgcn_s_setprio(2);
         else if (hw_wave >= 4) __builtin_amdgcn_s_setprio(1);
       }
-      const uint32_t(*cs)[CMD_WORDS] = cmd[s];
-      const uint32_t w0a = cs[4 * g + r][0], w0b = cs[4 * g + r + 2][0];
       const uint32_t wh = hsel ? w0b : w0a;
       // apply sub-step s-1 to the images: one history bit per observer, or a freshly dealt board
       if (head && !cmd_deal(wh) && cmd_hist_bit1(wh)) {
@@ -552,6 +579,7 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
           else if (d.x == 0x12345678u) __builtin_nontemporal_store(d, reinterpret_cast<brl_u32x4 *>(dst + 960 * k));  // timing experiment: no stores
         }
       }
+      if (s < 2) FS_STAMP(13 + s);  // store issue of slots 0, 1
     }
   }
 #ifdef BRL_TIMING
@@ -576,6 +604,8 @@ __global__ __launch_bounds__(FS_NW * 64) void k_rollout_fs(RolloutArgs A) {
     } else if (w < 11) {
       const uint32_t d13 = oimg[t][w - 7][13], d14 = oimg[t][w - 7][14];
       v = ((uint64_t)d14 << 24) | (uint64_t)((d13 >> 8) & 0xFFFFF0u);
+    } else if (w == W_SC) {
+      v = *reinterpret_cast<const uint64_t *>(&raw[total][t][0]);
     } else {
       v = img64[i];
     }

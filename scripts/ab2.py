@@ -106,7 +106,8 @@ def main():
                     d = json.loads(r.stdout.strip().splitlines()[-1])
                     res[name].append(d["us"]); sha[name] = d["sha"]; extra.setdefault(name, []).append((d["iso"], d["step"], d.get("fused")))
                 except Exception:
-                    print(name, "FAILED", r.stderr[-800:])
+                    print(name, "FAILED", r.returncode, r.stderr[-800:])
+                    sys.exit(1)   # nothing more on the card after a failed run
         base = sha.get(variants[0][0])
         for name, _ in variants:
             v = sorted(res[name])

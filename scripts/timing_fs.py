@@ -1,10 +1,13 @@
 """Timing build (-DBRL_TIMING) of k_rollout_fs: per-wave length, emit waves' time spent waiting for the logic wave, and stamps
-(cycles since wave start) at slots 0, 8, 16, 24, 32 of the logic wave and of the emit waves.  NBUF rotating output buffers."""
+(cycles since wave start) at slots 0, 8, 16, 24, 32 of the logic wave and of the emit waves, and for the first slots: when
+raw_posted / posted reach 2 and 3 and when each emit wave issues the stores of slots 0 and 1.  NBUF rotating output buffers.
+TIMING_SO=<path>: use a timing build made beforehand instead of compiling one."""
 import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-so = "/tmp/libbrl_timing_fs.so"
-subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-DBRL_TIMING"]
+so = os.environ.get("TIMING_SO", "/tmp/libbrl_timing_fs.so")   # TIMING_SO: a timing build made beforehand (same flags as below)
+if "TIMING_SO" not in os.environ:
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-DBRL_TIMING"]
                       + os.environ.get("FLAGS", "").split() + ["-o", so] + sorted(__import__("glob").glob(os.path.join(ROOT, "brl_amd/csrc/*.hip"))), stderr=subprocess.DEVNULL)   # (every unit of the library)
 from brl_amd import _capi
 _capi.LIB_PATH = so
@@ -43,9 +46,10 @@ names = ["logic", "loader/mask", "scorerA"] + [f"emit{g}" for g in range(8)] + [
 print("role          total(mean/p95)   wait(mean)   stamps (mean over workgroups, cycles/100)")
 for w in range(NW):
     m = tl[:, w].mean(0)
-    stamps = " ".join(f"{int(x) // 100:4d}" for x in m[:9] if x > 0) + "  | prologue: philox %d loads %d images %d barrier %d" % tuple(int(x) for x in m[9:13])
+    stamps = " ".join(f"{int(x) // 100:4d}" for x in m[:9] if x > 0) + "  | prologue: philox %d loads %d images %d barrier %d" % tuple(int(x) for x in m[9:13]) + "  | first slots: %d %d" % tuple(int(x) for x in m[13:15])
     print(f"{names[w]:12s} {d[:, w, 0].mean() / 100:6.0f} /{np.percentile(d[:, w, 0], 95) / 100:6.0f}   {d[:, w, 1].mean() / 100:6.0f}       {stamps}")
 rt = full[nblk * NW * 2:].reshape(nblk, NW, 32)[:, :, 30]
+print("first slots = logic: raw_posted reaches 2, 3 (1: its slot-0 stamp); prep: posted reaches 2, 3 (1: its slot-0 stamp); emit: stores of slots 0, 1 issued")
 print("shader clock: %.2f GHz (cycles / 100 MHz ticks of the slowest wave); launch = %.1f us by that wave's realtime" % (
     (d[..., 0].max(1) / np.maximum(rt.max(1), 1)).mean() * 0.1, rt.max(1).mean() / 100.0))
 print("slowest wave per workgroup: mean %.0f p95 %.0f max %.0f" % tuple(x / 100 for x in (d[..., 0].max(1).mean(), np.percentile(d[..., 0].max(1), 95), d[..., 0].max())))
