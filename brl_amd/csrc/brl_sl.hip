@@ -143,7 +143,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_sl_loss(const float *logits, i
   __shared__ float zt[LOSS_THREADS * NA];
   __shared__ uint8_t mt[LOSS_THREADS * NA];
   const int tid = (int)threadIdx.x;
-  const float inv38B = 1.0f / (38.0f * (float)B), invB = 1.0f / (float)B;
   double s_tgt = 0.0, s_ent = 0.0, s_acc = 0.0, s_ill = 0.0;  // per thread, in sample order
   for (int64_t base = 0; base < B; base += LOSS_THREADS) {
     const int rows = (int)((B - base < LOSS_THREADS) ? B - base : LOSS_THREADS);
@@ -156,7 +155,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_sl_loss(const float *logits, i
     __syncthreads();
     if (tid >= rows) continue;
     const int64_t b = base + tid;
-    // four passes over the row (re-read from LDS, not held in registers): maxima / legal bits, sums, terms, derivative
+    // passes over the row (re-read from LDS, not held in registers): maxima / legal bits, sums, terms; the derivative's two
     const float *lg = zt + tid * NA;
     const uint8_t *mk = mt + tid * NA;
     int y = label[b];
@@ -199,17 +198,35 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_sl_loss(const float *logits, i
     s_ill += (double)ill;
     if (dlogits != nullptr) {
       // d/dz_j of -mean(onehot * log_softmax) over [B, 38]: (softmax_j - onehot_j) / (38 B); of -ent_coef * mean(H): ent_coef
-      // * p_j (log p_j + H) / B on legal j (an illegal logit sits at finfo.min: its probability and derivative are 0)
+      // * p_j (log p_j + H) / B on legal j (an illegal logit sits at finfo.min: its probability and derivative are 0).
+      // In float64, rounded once at the store: softmax_y - 1 on a row the network is sure of, and log p_j + H on a flat row,
+      // cancel to float32's rounding noise, and a row's derivative is then wrong at ITS scale however small the batch's error.
+      // The sums are taken again (the float32 ones above stay what the metrics are made of): H = log s - sum e_j a_j / s.
+      const double dmx2 = (double)mx2, dmx = (double)mx;
+      double ds2 = 0.0, ds = 0.0, dea = 0.0;
 #pragma unroll 2
       for (int j = 0; j < NA; j++) {
-        const float z = lg[j];
+        const double z = (double)lg[j];
+        ds2 += exp(z - dmx2);
+        if ((lm >> j) & 1ull) {
+          const double a = z - dmx, e = exp(a);
+          ds += e;
+          dea += !(e <= 0.0) ? e * a : 0.0;  // 0 log 0 = 0, a NaN stays
+        }
+      }
+      const double dlse2 = log(ds2), dlse = log(ds);
+      const double dH = dlse - dea / ds;
+      const double d38B = 1.0 / (38.0 * (double)B), dB = (double)ent_coef / (double)B;
+#pragma unroll 2
+      for (int j = 0; j < NA; j++) {
+        const double z = (double)lg[j];
         const bool legal = (lm >> j) & 1ull;
-        const float p2 = expf((z - mx2) - lse2);
-        const float lsm = (z - mx) - lse;
-        const float p = legal ? expf(lsm) : 0.0f;
-        const float dt = (p2 - ((j == y) ? 1.0f : 0.0f)) * inv38B;
-        const float de = legal ? ent_coef * invB * (p * (lsm + H)) : 0.0f;
-        dlogits[b * NA + j] = dt + de;
+        const double p2 = exp((z - dmx2) - dlse2);
+        const double lsm = (z - dmx) - dlse;
+        const double p = legal ? exp(lsm) : 0.0;
+        const double dt = (p2 - ((j == y) ? 1.0 : 0.0)) * d38B;
+        const double de = legal ? dB * (p * (lsm + dH)) : 0.0;
+        dlogits[b * NA + j] = (float)(dt + de);
       }
     }
   }

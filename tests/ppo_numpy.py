@@ -110,32 +110,40 @@ def loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob, gae,
     / 2), grads like params): `head_loss` on the forward pass and the backward pass written out."""
     logits, value, hs, zs, dacts = forward(params, obs.astype(np.float64), activation, gate_fn)
     total, aux, dlogits, dv = head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tgt)
+    return total, aux, backward(params, dlogits, dv, hs, dacts)
+
+
+def backward(params, dlogits, dvalue, hs, dacts):
+    """the DeepMind MLP's backward pass written out: d loss / d logits [B, 38], d loss / d value [B] and `forward`'s tape (hs, dacts)
+    -> grads like params"""
     grads = [None] * len(params)
     h = hs[-1]
     grads[-2] = (dlogits.T @ h, dlogits.sum(0))
-    grads[-1] = (dv[None, :] @ h, np.array([dv.sum()]))
-    dh = dlogits @ params[-2][0] + dv[:, None] * params[-1][0]
+    grads[-1] = (dvalue[None, :] @ h, np.array([dvalue.sum()]))
+    dh = dlogits @ params[-2][0] + dvalue[:, None] * params[-1][0]
     for k in range(len(params) - 3, -1, -1):
         dz = dh * dacts[k]
         grads[k] = (dz.T @ hs[k], dz.sum(0))
         dh = dz @ params[k][0]
-    return total, aux, grads
+    return grads
 
 
 def global_norm(grads):
     return float(np.sqrt(sum((gw ** 2).sum() + (gb ** 2).sum() for gw, gb in grads)))
 
 
-def adam_step(cfg, t, params, m, v, grads, lr=None):
+def adam_step(cfg, t, params, m, v, grads, lr=None, eps=1e-5, clip=None):
     """step t (1, 2, ...) of clip_by_global_norm(max_grad_norm) + Adam(eps=1e-5) (ppo.py:195-211) with torch's arithmetic
     (torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6) clamped to 1; torch.optim.Adam: m <- m + (g - m)(1 - b1),
     v <- b2 v + (1 - b2) g^2, p <- p - lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)).  params / m / v / grads: lists of
-    (W, b) pairs -> (params, m, v, pre-clip global norm)."""
+    (W, b) pairs -> (params, m, v, pre-clip global norm).  eps: Adam's; clip: None = as cfg says, False = no clipping (cfg may
+    then be None with lr given) — brl_amd.sl.make_optimizer is adam_step(None, t, ..., lr=lr, eps=1e-8, clip=False)."""
     lr = cfg["lr"] if lr is None else lr
-    b1, b2, eps = 0.9, 0.999, 1e-5
+    b1, b2 = 0.9, 0.999
     gn = global_norm(grads)
+    clip = cfg.get("global_gradient_clipping", True) if clip is None else clip
     # (np.minimum, as torch.clamp and jnp.minimum: a NaN norm gives a NaN factor; Python's min(1.0, nan) is 1.0)
-    scale = float(np.minimum(1.0, cfg["max_grad_norm"] / (gn + 1e-6))) if cfg.get("global_gradient_clipping", True) else 1.0
+    scale = float(np.minimum(1.0, cfg["max_grad_norm"] / (gn + 1e-6))) if clip else 1.0
     bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
     P, M, V = [], [], []
     for pp, mm, vv, gg in zip(params, m, v, grads):
@@ -234,13 +242,19 @@ def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob,
     """-> (total, aux, grads like params): the loss of `head_loss` on the FAIR forward pass (`fair_forward`; gate_fn: see there)
     and its gradient by reverse-mode differentiation of the reference's own statement order (a tape of (kind, ...) entries; no
     shared code with the build)."""
-    _, dact = _act(activation)
     logits, value, x, tape = fair_forward(params, obs, activation, gate_fn)
     total, aux, dlogits, dv = head_loss(cfg, logits, value, mask, action, old_value, old_log_prob, gae, tgt)
+    return total, aux, fair_backward(params, dlogits, dv, x, tape, activation)
+
+
+def fair_backward(params, dlogits, dvalue, x, tape, activation="relu"):
+    """the FAIR net's backward pass: d loss / d logits [B, 38], d loss / d value [B], the heads' input x and `fair_forward`'s tape
+    -> grads like params"""
+    _, dact = _act(activation)
     grads = [None] * len(params)
     grads[11] = (dlogits.T @ x, dlogits.sum(0))
-    grads[12] = (dv[None, :] @ x, np.array([dv.sum()]))
-    d = dlogits @ params[11][0] + dv[:, None] * params[12][0]
+    grads[12] = (dvalue[None, :] @ x, np.array([dvalue.sum()]))
+    d = dlogits @ params[11][0] + dvalue[:, None] * params[12][0]
     # the shortcuts were taken right AFTER the linear layers 0 and 6 (s1, s3) and after the first / third block's sum (s2, s4):
     # a pending shortcut gradient is added where its value was defined
     pending = {}
@@ -266,4 +280,4 @@ def fair_loss_and_grads(cfg, params, obs, mask, action, old_value, old_log_prob,
             grads[k] = (d.T @ v, d.sum(0))
             d = d @ params[k][0]
     assert not pending
-    return total, aux, grads
+    return grads

@@ -1,6 +1,14 @@
-"""Synthetic trajectory files for the supervised pre-trainer's tests (brl_amd/sl.py) and a numpy restatement of its example
-stream (brl_sl_sample, include/brl_sl.h).  No dataset is needed: deals are random, auctions are random legal ones or follow a
-simple teacher."""
+"""Synthetic trajectory files for the supervised pre-trainer's tests (brl_amd/sl.py) and the host restatements they check it
+against.  No dataset is needed: deals are random, auctions are random legal ones or follow a simple teacher.
+
+* ``sample``: the example stream (brl_sl_sample, include/brl_sl.h) in numpy.
+* ``host_batch``: the observation rows, legal masks and labels of given (trajectory, call index) pairs through the oracle.
+* ``loss64``: sl.py's loss, its metrics and d total / d logits in float64; ``loss32``: the same formulas in numpy float32, the
+  reference's own precision — the yardstick of the loss kernel's per-row derivative bound.
+* ``logits64`` / ``sl_step64``: one supervised step in float64 — the forward of tests/ppo_numpy.py, ``loss64``, the written-out
+  backward with no value gradient -> the metrics row and the gradients (checked against torch autograd in float64 by
+  tests/test_sl_host.py); ``top_two_gap`` for the rows whose argmax fp32 may decide otherwise.
+"""
 import numpy as np
 
 PASS, X, XX = 0, 1, 2
@@ -174,3 +182,95 @@ def loss64(logits, label, mask, ent_coef):
     out = np.array([tgt - ent_coef * H.mean(), tgt, H.mean(), (np.argmax(z, 1) == label).mean(), (p2 * ~m).sum(1).mean()])
     d = (p2 - onehot) / (38 * B) + ent_coef * np.where(m, p * (np.where(m, lsm, 0.0) + H[:, None]), 0.0) / B
     return out, d
+
+
+def loss32(logits, label, mask, ent_coef):
+    """`loss64`'s formulas evaluated in numpy float32 throughout (the reference computes in float32) -> (out[5], dlogits), float32"""
+    f = np.float32
+    z = np.asarray(logits, f)
+    B = z.shape[0]
+    m = np.asarray(mask, bool)
+    onehot = np.zeros_like(z)
+    onehot[np.arange(B), label] = f(1.0)
+    ls2 = z - z.max(1, keepdims=True)
+    ls2 = ls2 - np.log(np.exp(ls2).sum(1, keepdims=True, dtype=f))
+    p2 = np.exp(ls2)
+    zm = np.where(m, z, f(-np.inf))
+    lsm = zm - zm.max(1, keepdims=True)
+    lsm = lsm - np.log(np.exp(lsm).sum(1, keepdims=True, dtype=f))
+    p = np.where(m, np.exp(lsm), f(0.0))
+    lsm0 = np.where(m, lsm, f(0.0))
+    plogp = np.where(p == 0, f(0.0), p * lsm0)
+    H = -plogp.sum(1, dtype=f)
+    tgt = -(onehot * ls2).mean(dtype=f)
+    Hm = H.mean(dtype=f)
+    out = np.array([tgt - f(ent_coef) * Hm, tgt, Hm, (np.argmax(z, 1) == label).mean(dtype=f), (p2 * ~m).sum(1, dtype=f).mean(dtype=f)], f)
+    d = (p2 - onehot) / f(38 * B) + f(ent_coef) * np.where(m, p * (lsm0 + H[:, None]), f(0.0)) / f(B)
+    assert out.dtype == f and d.dtype == f
+    return out, d
+
+
+# ---- the examples of given (trajectory, call index) pairs through the oracle ---------------------------------------------------
+def host_batch(ts, traj, pos, oracle):
+    """(obs float32 [B, 480], mask uint8 [B, 38], label int32 [B]) of examples (traj[i], pos[i]) of the TrajectorySet `ts`: the
+    converted deal (seat s holds the cards of its hand bits), dealer 0, nobody vulnerable, identity seating; the oracle steps each
+    trajectory's calls and is observed for the seat to act before call pos[i].  Every trajectory is stepped through its largest
+    requested call: the auction is over behind that call exactly where it is the trajectory's last."""
+    from brl_amd import sl_data
+    traj, pos = np.asarray(traj, np.int64), np.asarray(pos, np.int64)
+    B = traj.shape[0]
+    obs, mask = np.zeros((B, 480), np.float32), np.zeros((B, 38), np.uint8)
+    nc_all = ts.n_calls()
+    assert B > 0 and (traj >= 0).all() and (traj < ts.n).all() and (pos >= 0).all() and (pos < nc_all[traj]).all()
+    uniq, inv = np.unique(traj, return_inverse=True)
+    last = np.zeros(uniq.size, np.int64)
+    np.maximum.at(last, inv, pos)
+    cards = np.arange(52)
+    hand = np.stack([np.concatenate([sl_data.openspiel_to_pgx_card(cards[((int(ts.hands[t, s]) >> cards) & 1) == 1]) for s in range(4)])
+                     for t in uniq])
+    st = oracle.init_explicit(hand, 0, 0, 0, [0, 1, 2, 3], np.zeros((uniq.size, 20), np.uint8))
+    nc, start = nc_all[uniq], ts.offsets[uniq]
+    for k in range(int(last.max()) + 1):
+        want = np.nonzero(pos == k)[0]
+        if want.size:
+            sub = st[inv[want]]
+            assert not sub["terminated"].any()
+            obs[want] = oracle.observe(sub, sub["current_player"]).astype(np.float32)
+            mask[want] = sub["legal_action_mask"]
+        live = np.nonzero(k <= last)[0]
+        sub = st[live]
+        oracle.step(sub, ts.calls[start[live] + k].astype(np.int32))
+        assert np.array_equal(sub["terminated"].astype(bool), k == nc[live] - 1), f"the auction's end is not at its last call (call {k})"
+        st[live] = sub
+    label = ts.calls[ts.offsets[traj] + pos].astype(np.int32)
+    return obs, mask, label
+
+
+# ---- one supervised step in float64 ---------------------------------------------------------------------------------------------
+def logits64(params, obs, activation, model, gate_fn=None):
+    """(logits, tape for `_backward`) of tests/ppo_numpy.forward (model "DeepMind...") or fair_forward ("FAIR") in float64"""
+    from tests import ppo_numpy as N
+    x = np.asarray(obs, np.float64)
+    if model == "FAIR":
+        logits, _, h, tape = N.fair_forward(params, x, activation, gate_fn)
+        return logits, (h, tape)
+    logits, _, hs, _, dacts = N.forward(params, x, activation, gate_fn)
+    return logits, (hs, dacts)
+
+
+def top_two_gap(logits):
+    """per row: the largest logit minus the second largest (0 at a tie)"""
+    s = np.sort(np.asarray(logits, np.float64), axis=1)
+    return s[:, -1] - s[:, -2]
+
+
+def sl_step64(params, obs, mask, label, ent_coef, activation, model, gate_fn=None):
+    """One step of brl_amd.sl.SLStep in float64 -> (metrics row [total, target, entropy, accuracy, illegal] of the forward on
+    `params`, grads like params): the forward, `loss64`, the factored backward of tests/ppo_numpy.py with d loss / d value = 0
+    (the value head takes no part in the supervised loss: its gradients are zeros)."""
+    from tests import ppo_numpy as N
+    logits, tape = logits64(params, obs, activation, model, gate_fn)
+    row, d = loss64(logits, np.asarray(label, np.int64), mask, ent_coef)
+    dv = np.zeros(logits.shape[0])
+    grads = N.fair_backward(params, d, dv, *tape, activation) if model == "FAIR" else N.backward(params, d, dv, *tape)
+    return row, grads
