@@ -142,6 +142,11 @@ extern "C" int brl_mlp_gemm_dh_heads_dw(int device, const float *dz, int64_t ldd
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
   NEED(aligned16(dz) && aligned16(w) && aligned16(out) && aligned16(gate) && (((uintptr_t)colsum) & 3) == 0,
        "dz / w / out / gate not 16-byte aligned (colsum: 4-byte)");
+  // the heads' dW role: h in 16-byte pieces, one float (int32) per access of everything else
+  NEED(aligned16(h), "h not 16-byte aligned");
+  NEED((((uintptr_t)dheads | (uintptr_t)dw_partials | (uintptr_t)db_partials | (uintptr_t)loss_partials | (uintptr_t)gram_partials |
+         (uintptr_t)row_index | (uintptr_t)stat_sums | (uintptr_t)gram_sums) & 3) == 0,
+       "dheads / dw_partials / db_partials / loss_partials / gram_partials / row_index / stat_sums / gram_sums not 4-byte aligned");
   NEED(batch > 0 && hidden > 0 && hidden % 256 == 0 && ldh >= hidden && ldh % 4 == 0, "batch / hidden (a multiple of 256) / ldh");
   NEED(dheads && h && dw_partials && db_partials, "NULL array");
   NEED(nsplit >= 1 && (batch + nsplit - 1) / nsplit <= 64, "nsplit: at most 64 rows per split");

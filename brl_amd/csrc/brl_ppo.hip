@@ -9,10 +9,32 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "abi_common.hpp"
 #include "nan_math.hpp"   // clamp_nan / min_nan / max_nan: `_loss_fn`'s clip, minimum and maximum keep a NaN
 
 static inline unsigned thread_grid(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+// the alignment include/brl_hip.h states for a pointer argument (NULL passes: whether it may be NULL is another check).  These
+// NEEDs stand in front of everything else an entry point does: a refusal reads nothing and launches nothing.
+static inline bool al(const void *p, uintptr_t bytes) { return (((uintptr_t)p) & (bytes - 1)) == 0; }
+static inline bool al4(std::initializer_list<const void *> ps) {
+  for (const void *p : ps)
+    if (!al(p, 4)) return false;
+  return true;
+}
+static inline bool al16(std::initializer_list<const void *> ps) {
+  for (const void *p : ps)
+    if (!al(p, 16)) return false;
+  return true;
+}
+// the finalize segments' partials[i] / out[i] (host arrays of device pointers): one float per load and per store
+static inline bool segs_al4(int nseg, const float *const *partials, float *const *out) {
+  if (nseg < 1 || nseg > 16 || !partials || !out) return true;   // (refused by the entry point's own check)
+  for (int i = 0; i < nseg; i++)
+    if (!al(partials[i], 4) || !al(out[i], 4)) return false;
+  return true;
+}
 
 // ---- PPO-clip loss and its gradient w.r.t. the network outputs, one launch (src/update.py:90-167) ------------
 // One wave per sample, lane a = action a.  Forward: masked log-softmax -> log-prob of the taken action, ratio,
@@ -243,6 +265,8 @@ extern "C" int brl_ppo_loss(int device, const float *logits, int64_t logits_stri
                             const float *targets, int64_t batch, float clip_eps, float vf_coef, float ent_coef, int masked,
                             int value_clipping, float *dlogits, float *dvalue, float *partials, float *illegal_probs,
                             void *stream) {
+  NEED(al4({logits, value, action, old_value, old_log_prob, gae, targets, dlogits, dvalue, partials, illegal_probs}),
+       "logits / value / action / old_value / old_log_prob / gae / targets / dlogits / dvalue / partials / illegal_probs not 4-byte aligned");
   NEED(batch > 0, "batch");
   NEED(logits && value && mask && action && old_value && old_log_prob && gae && targets, "NULL input array");
   NEED(dlogits && dvalue && partials, "NULL output array");
@@ -259,6 +283,10 @@ extern "C" int brl_mb_gather_bind(int device, const brl_transition *flat, const 
                                   const int32_t *mb_index, int64_t mbs, float *x0, uint8_t *mask, int32_t *action, float *old_value,
                                   float *old_log_prob, float *gae_out, float *targets_out, int64_t nsteps, void *args_dev,
                                   void *stream) {
+  NEED(al(x0, 16) && al(args_dev, 8) && al(perm, 8), "x0 not 16-byte aligned / perm, args_dev: 8-byte");
+  NEED(!flat || al4({flat->obs, flat->action, flat->value, flat->log_prob}), "trajectory: obs / action / value / log_prob not 4-byte aligned");
+  NEED(al4({adv, targets, mb_index, action, old_value, old_log_prob, gae_out, targets_out}),
+       "adv / targets / mb_index / action / old_value / old_log_prob / gae_out / targets_out not 4-byte aligned");
   NEED(flat && flat->obs && flat->legal_action_mask && flat->action && flat->value && flat->log_prob, "trajectory");
   NEED(adv && targets && perm && mb_index && mbs > 0, "adv / targets / perm / mb_index / mbs");
   NEED(x0 && mask && action && old_value && old_log_prob && gae_out && targets_out && args_dev, "NULL output array / args_dev");
@@ -273,6 +301,7 @@ extern "C" int brl_mb_gather_bind(int device, const brl_transition *flat, const 
 }
 
 extern "C" int brl_mb_gather_dev(int device, const void *args_dev, int64_t mbs, void *stream) {
+  NEED(al(args_dev, 8), "args_dev not 8-byte aligned");
   NEED(args_dev && mbs > 0, "args_dev / mbs");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_mb_gather_dev, dim3((unsigned)mbs), dim3(128), 0, (hipStream_t)stream, (const GatherArgs *)args_dev);
@@ -282,6 +311,7 @@ extern "C" int brl_mb_gather_dev(int device, const void *args_dev, int64_t mbs, 
 
 extern "C" int brl_act_bwd_colsum(int device, float *dh, const float *h, int64_t rows, int64_t cols, int64_t ld, int act,
                                   float *scratch, void *stream) {
+  NEED(al16({dh, h, scratch}), "dh / h / scratch not 16-byte aligned");
   NEED(dh && h && scratch && rows > 0 && cols > 0 && ld >= cols, "dh / h / scratch / rows / cols / ld");
   NEED(cols % 4 == 0 && ld % 4 == 0, "cols and ld multiples of 4");
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
@@ -298,6 +328,9 @@ extern "C" int brl_act_bwd_colsum_heads_dw(int device, float *dz, const float *h
                                            int64_t hidden, int nsplit, float *dw_partials, float *db_partials,
                                            const float *loss_partials, const float *gram_partials, int64_t ngroups,
                                            const int32_t *row_index, float *stat_sums, float *gram_sums, void *stream) {
+  NEED(al16({dz, hh, scratch, h}), "dz / hh / scratch / h not 16-byte aligned");
+  NEED(al4({dheads, dw_partials, db_partials, loss_partials, gram_partials, row_index, stat_sums, gram_sums}),
+       "dheads / dw_partials / db_partials / loss_partials / gram_partials / row_index / stat_sums / gram_sums not 4-byte aligned");
   NEED(dz && hh && scratch && rows > 0 && cols > 0 && ld >= cols, "dz / h / scratch / rows / cols / ld");
   NEED(cols % 4 == 0 && ld % 4 == 0, "cols and ld multiples of 4");
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
@@ -323,6 +356,7 @@ extern "C" int brl_act_bwd_colsum_heads_dw(int device, float *dz, const float *h
 
 extern "C" int brl_bias_finalize_ex(int device, int nseg, const float *const *partials, const int64_t *cols, const int64_t *tiles,
                                     float *const *out, void *stream) {
+  NEED(segs_al4(nseg, partials, out), "partials[i] / out[i] not 4-byte aligned");
   NEED(nseg >= 1 && nseg <= BIAS_MAX_SEGS && partials && cols && tiles && out, "nseg / partials / cols / tiles / out");
   HIP_TRY(hipSetDevice(device));
   BiasSegs S{};
@@ -340,6 +374,7 @@ extern "C" int brl_bias_finalize_ex(int device, int nseg, const float *const *pa
 
 extern "C" int brl_bias_finalize_rows(int device, int nseg, const float *const *partials, const int64_t *cols, const int64_t *tiles,
                                       float *const *out, int first_row_seg, const int32_t *row_index, void *stream) {
+  NEED(segs_al4(nseg, partials, out) && al(row_index, 4), "partials[i] / out[i] / row_index not 4-byte aligned");
   NEED(nseg >= 1 && nseg <= BIAS_MAX_SEGS && partials && cols && tiles && out, "nseg / partials / cols / tiles / out");
   NEED(first_row_seg >= 0 && first_row_seg <= nseg && (row_index || first_row_seg == nseg), "first_row_seg / row_index");
   HIP_TRY(hipSetDevice(device));
@@ -369,6 +404,9 @@ extern "C" int brl_fair_chain(int device, const brl_fair_net *net, const float *
                               const float *old_value, const float *old_log_prob, const float *gae, const float *targets,
                               int64_t batch, float clip_eps, float vf_coef, float ent_coef, int masked, int value_clipping,
                               int reward_scaling, int act, const brl_fair_work *work, void *stream) {
+  NEED(al4({action, old_value, old_log_prob, gae, targets}), "action / old_value / old_log_prob / gae / targets not 4-byte aligned");
+  NEED(!net || al(net->head_b, 4), "net: head_b not 4-byte aligned");
+  NEED(!work || al16({work->dheads, work->partials, work->gram_partials}), "work: dheads / partials / gram_partials not 16-byte aligned");
   NEED(net && work && x0 && mask && action && old_value && old_log_prob && gae && targets, "NULL input");
   NEED(batch > 0 && batch % fair::R == 0, "batch (a multiple of 16)");
   NEED(act == 0 || act == 1, "act");
@@ -378,7 +416,7 @@ extern "C" int brl_fair_chain(int device, const brl_fair_net *net, const float *
     NEED((((uintptr_t)net->w[l]) & 15) == 0 && (((uintptr_t)net->b[l]) & 15) == 0, "net: 16-byte alignment");
     A.net.w[l] = net->w[l]; A.net.b[l] = net->b[l];
   }
-  NEED(net->head_w && net->head_b && (((uintptr_t)net->head_w) & 15) == 0, "net: heads");
+  NEED(net->head_w && net->head_b && (((uintptr_t)net->head_w) & 15) == 0, "net: heads (head_w: 16-byte alignment)");
   A.net.wh = net->head_w; A.net.bh = net->head_b;
   NEED(work->inp && work->dzs && work->gates && work->cat6 && work->x4 && work->dz0 && work->dz6 && work->dheads && work->tiles &&
        work->partials, "work: NULL array");
@@ -400,6 +438,7 @@ extern "C" int brl_fair_chain(int device, const brl_fair_net *net, const float *
 
 extern "C" int brl_fair_forward(int device, const brl_fair_net *net, const float *x, int64_t rows, int act, float *logits, float *value,
                                 void *stream) {
+  NEED(al4({logits, value}) && (!net || al(net->head_b, 4)), "logits / value / net->head_b not 4-byte aligned");
   NEED(net && x && logits && value, "NULL array");
   NEED(rows >= 0 && rows < (1ll << 31), "rows");
   NEED(act == 0 || act == 1, "act");
@@ -430,6 +469,9 @@ extern "C" int brl_ppo_heads_loss_split(int device, const float *h, int64_t ldh,
                                         float clip_eps, float vf_coef, float ent_coef, int masked, int value_clipping,
                                         int reward_scaling, float *heads_out, float *dheads, float *partials, float *gram_partials,
                                         float *head_parts, int ksplit, void *stream) {
+  NEED(al16({h, head_w}), "h / head_w not 16-byte aligned");
+  NEED(al4({head_b, action, old_value, old_log_prob, gae, targets, heads_out, dheads, partials, gram_partials, head_parts}),
+       "head_b / action / old_value / old_log_prob / gae / targets / heads_out / dheads / partials / gram_partials / head_parts not 4-byte aligned");
   NEED(batch > 0 && hidden > 0 && hidden % 16 == 0 && ldh >= hidden && ldh % 4 == 0, "batch / hidden (a multiple of 16) / ldh");
   NEED(h && head_w && head_b && mask && action && old_value && old_log_prob && gae && targets, "NULL input array");
   NEED(dheads && partials && head_parts, "NULL output array");
@@ -454,6 +496,9 @@ extern "C" int brl_ppo_heads_bwd(int device, const float *dheads, const float *h
                                  int64_t hidden, int act, int nsplit, float *dw_partials, float *db_partials, float *dh,
                                  float *tile_sums, const float *loss_partials, const float *gram_partials, int64_t ngroups,
                                  const int32_t *row_index, float *stat_sums, float *gram_sums, void *stream) {
+  NEED(al16({h, head_w, dh, tile_sums}), "h / head_w / dh / tile_sums not 16-byte aligned");
+  NEED(al4({dheads, dw_partials, db_partials, loss_partials, gram_partials, row_index, stat_sums, gram_sums}),
+       "dheads / dw_partials / db_partials / loss_partials / gram_partials / row_index / stat_sums / gram_sums not 4-byte aligned");
   NEED(batch > 0 && hidden > 0 && hidden % 256 == 0 && ldh >= hidden && ldh % 4 == 0, "batch / hidden (a multiple of 256) / ldh");
   NEED(dheads && h && head_w && dh && tile_sums && (!dw_partials == !db_partials), "NULL array");
   const bool with_dw = dw_partials != nullptr;   // NULL: the weight-gradient role is launched elsewhere (brl_act_bwd_colsum_heads_dw)
@@ -481,6 +526,7 @@ extern "C" int brl_ppo_heads_bwd(int device, const float *dheads, const float *h
 extern "C" int brl_ppo_stats_gram(int device, const float *partials, int64_t npartials, int64_t batch, const float *gram_partials,
                                   int64_t ngram, float vf_coef, float ent_coef, float illegal_coef, float *out_rows,
                                   const int32_t *row_index, float *vec_out, void *stream) {
+  NEED(al4({partials, gram_partials, out_rows, row_index, vec_out}), "partials / gram_partials / out_rows / row_index / vec_out not 4-byte aligned");
   NEED(partials && out_rows && npartials > 0 && batch > 0, "partials / out_rows / npartials / batch");
   NEED(gram_partials && ngram > 0, "gram_partials / ngram");
   HIP_TRY(hipSetDevice(device));
@@ -492,6 +538,7 @@ extern "C" int brl_ppo_stats_gram(int device, const float *partials, int64_t npa
 
 extern "C" int brl_ppo_illegal_grad(int device, const float *heads, const uint8_t *mask, const float *vec, float illegal_coef,
                                     int64_t batch, float *dheads, void *stream) {
+  NEED(al4({heads, vec, dheads}), "heads / vec / dheads not 4-byte aligned");
   NEED(heads && mask && vec && dheads && batch > 0, "heads / mask / vec / dheads / batch");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_illegal_grad, dim3(thread_grid(batch, 4)), dim3(256), 0, (hipStream_t)stream, heads, mask, vec, illegal_coef,
@@ -502,6 +549,7 @@ extern "C" int brl_ppo_illegal_grad(int device, const float *heads, const uint8_
 
 extern "C" int brl_ppo_stats_rows(int device, const float *stat_sums, const float *gram_sums, int64_t rows, int64_t batch, float vf_coef,
                                   float ent_coef, float illegal_coef, float *out_rows, void *stream) {
+  NEED(al4({stat_sums, gram_sums, out_rows}), "stat_sums / gram_sums / out_rows not 4-byte aligned");
   NEED(stat_sums && gram_sums && out_rows && rows > 0 && batch > 0, "stat_sums / gram_sums / out_rows / rows / batch");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_ppo_stats2, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, stat_sums, (int64_t)1, batch, gram_sums,
@@ -517,6 +565,9 @@ extern "C" int brl_adam_clip_fin_gather(int device, float *p, float *g, float *m
                                         int64_t scratch_len, int32_t *mb_index, float *norm_out, const void *gather_args, int64_t mbs,
                                         int nseg, const float *const *partials, const int64_t *cols, const int64_t *tiles,
                                         float *const *out, void *stream) {
+  NEED(al16({p, g, m, v}) && al(gather_args, 8), "p / g / m / v not 16-byte aligned / gather_args: 8-byte");
+  NEED(al4({step, lr_dev, scratch, mb_index, norm_out}) && segs_al4(nseg, partials, out),
+       "step / lr_dev / scratch / mb_index / norm_out / partials[i] / out[i] not 4-byte aligned");
   NEED(nseg >= 1 && nseg <= BIAS_MAX_SEGS && partials && cols && tiles && out, "nseg / partials / cols / tiles / out");
   NEED(p && g && m && v && step && scratch && n > 0 && n % 4 == 0, "p / g / m / v / step / scratch / n (a multiple of 4)");
   NEED(!gather_args || (mb_index && mbs > 0), "gather_args needs mb_index and the minibatch size");
@@ -568,6 +619,7 @@ static int shard_geom(const brl_shard_geom *geom, int rank_lo, int rank_hi, Shar
 
 extern "C" int brl_adam_shard_norm(int device, const float *g, const brl_shard_geom *geom, int rank_lo, int rank_hi, float grad_scale,
                                    float *partials, float *step, int32_t *mb_index, void *stream) {
+  NEED(al(g, 16) && al4({partials, step, mb_index}), "g not 16-byte aligned / partials, step, mb_index: 4-byte");
   NEED(g && partials && step, "g / partials / step");
   ShardGeom G;
   if (int rc = shard_geom(geom, rank_lo, rank_hi, &G)) return rc;
@@ -582,6 +634,8 @@ extern "C" int brl_adam_shard_apply(int device, float *p, const float *g, float 
                                     int rank_hi, const float *partials, const float *step, float lr, const float *lr_dev, float beta1,
                                     float beta2, float eps, float max_norm, float grad_scale, float *norm_out, const void *gather_args,
                                     int64_t mbs, void *stream) {
+  NEED(al16({p, g, m, v}) && al(gather_args, 8), "p / g / m / v not 16-byte aligned / gather_args: 8-byte");
+  NEED(al4({partials, step, lr_dev, norm_out}), "partials / step / lr_dev / norm_out not 4-byte aligned");
   NEED(p && g && m && v && partials && step, "p / g / m / v / partials / step");
   NEED(!gather_args || mbs > 0, "gather_args needs the minibatch size");
   ShardGeom G;
@@ -600,6 +654,7 @@ extern "C" int brl_adam_shard_apply(int device, float *p, const float *g, float 
 
 extern "C" int brl_ppo_stats(int device, const float *partials, int64_t batch, const float *gram, float vf_coef,
                              float ent_coef, float *out, void *stream) {
+  NEED(al4({partials, gram, out}), "partials / gram / out not 4-byte aligned");
   NEED(partials && out && batch > 0, "partials / out / batch");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(512), 0, (hipStream_t)stream, partials, (int64_t)thread_grid(batch, 4), batch,

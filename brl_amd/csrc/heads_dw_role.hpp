@@ -86,10 +86,11 @@ __device__ __forceinline__ void heads_bwd_dw_block(const HeadsBwdArgs &A, const 
     // the split's 64 x 64 tile of h and its d(heads) rows go through LDS; ALL of the thread's global loads are issued
     // before anything waits (each byte is read once: the kernel is bound by load latency, not by bytes)
     float4 hv4[4];
+    const int64_t hb0 = (nb > 0) ? b0 : 0;   // (a split behind the last row — nsplit > batch — reads row 0, not a row h does not have)
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const int rr = (tid >> 4) + 16 * u;   // 16 threads per row of 64 floats
-      hv4[u] = *reinterpret_cast<const float4 *>(A.h + (b0 + ((rr < nb) ? rr : 0)) * A.ldh + jt * HB_JT + 4 * (tid & 15));
+      hv4[u] = *reinterpret_cast<const float4 *>(A.h + (hb0 + ((rr < nb) ? rr : 0)) * A.ldh + jt * HB_JT + 4 * (tid & 15));
       if (rr >= nb) hv4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     constexpr int DPT = (64 * HD_NOUT + 255) / 256;   // d(heads) elements per thread

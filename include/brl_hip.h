@@ -366,7 +366,8 @@ int brl_eval_reduce(brl_handle *h, int64_t n, const brl_table_info *table_a, con
  * / d(logits, value) with the 1/batch of the means folded in; partials float [ceil(batch/4), 8]: per-block sums of
  * (value-loss term, actor-loss term, entropy, approx-KL term, clipped?) — column sums / batch are the logged
  * statistics; illegal_probs float [batch,38] (may be NULL): softmax(logits) * ~mask (:136-137).
- * No handle: `device` is the HIP device the arrays live on. */
+ * No handle: `device` is the HIP device the arrays live on.
+ * Alignment: every float / int32 array 4-byte aligned (one element per load and per store), mask any; BRL_E_ARG otherwise. */
 int brl_ppo_loss(int device, const float *logits, int64_t logits_stride, const float *value, const uint8_t *mask,
                  const int32_t *action, const float *old_value, const float *old_log_prob, const float *gae,
                  const float *targets, int64_t batch, float clip_eps, float vf_coef, float ent_coef, int masked,
@@ -375,7 +376,8 @@ int brl_ppo_loss(int device, const float *logits, int64_t logits_stride, const f
 /* The logged statistics of that minibatch step (src/update.py:142-167), one launch: partials as written by brl_ppo_loss
  * for `batch` samples; gram = P^T P (row-major float [38,38], may be NULL) of P = illegal_probs, from which
  * `jnp.linalg.norm(P, ord=2) / 2` (:138-141) is obtained without an SVD (8 squarings + Rayleigh quotient).
- * out: float [8] = total_loss, value_loss, loss_actor, entropy, approx_kl, clipfrac, illegal-action norm / 2, 0. */
+ * out: float [8] = total_loss, value_loss, loss_actor, entropy, approx_kl, clipfrac, illegal-action norm / 2, 0.
+ * partials, gram and out 4-byte aligned (one float per access). */
 int brl_ppo_stats(int device, const float *partials, int64_t batch, const float *gram, float vf_coef, float ent_coef,
                   float *out, void *stream);
 
@@ -392,7 +394,10 @@ int brl_ppo_stats(int device, const float *partials, int64_t batch, const float 
  * parts added in order.  Outputs: dheads float [batch,39] = d(total)/d(heads); partials float [ceil(batch / 4) * 8] for
  * brl_ppo_stats_gram; gram_partials (may be NULL) float [ceil(batch / 4) * 1444]: per 4-sample group, P^T P of its
  * illegal-action probabilities (src/update.py:136-141); heads_out (may be NULL) float [batch,39].  reward_scaling != 0: the
- * advantages are normalised over the minibatch first, (gae - mean) / (std + 1e-8) with jnp's ddof = 0 (src/update.py:31-44,118). */
+ * advantages are normalised over the minibatch first, (gae - mean) / (std + 1e-8) with jnp's ddof = 0 (src/update.py:31-44,118).
+ * Alignment: h and head_w 16-byte aligned (the product fetches whole 16-byte pieces of their rows; with ldh and hidden multiples
+ * of 4 every row then starts on one); head_b, action, the float columns and every output (heads_out, dheads, partials,
+ * gram_partials, head_parts) 4-byte, mask any; BRL_E_ARG otherwise. */
 int brl_ppo_heads_loss_split(int device, const float *h, int64_t ldh, const float *head_w, const float *head_b, int64_t hidden,
                        const uint8_t *mask, const int32_t *action, const float *old_value, const float *old_log_prob,
                        const float *gae, const float *targets, int64_t batch, float clip_eps, float vf_coef, float ent_coef,
@@ -408,7 +413,10 @@ int brl_ppo_heads_loss_split(int device, const float *h, int64_t ldh, const floa
  * gram_sums != NULL: the same launches also add up brl_ppo_heads_loss_split's loss_partials float [ngroups,8] and gram_partials float
  * [ngroups,1444] (in group order) into row *row_index (device memory) of stat_sums float [rows,8] / gram_sums float [rows,1444]:
  * the statistics of a whole update are then formed by ONE brl_ppo_stats_rows at its end instead of a launch per step. */
-/* (dw_partials = db_partials = NULL: only the activation-gradient role is launched — see brl_act_bwd_colsum_heads_dw) */
+/* (dw_partials = db_partials = NULL: only the activation-gradient role is launched — see brl_act_bwd_colsum_heads_dw)
+ * nsplit may exceed the splits the batch fills: the partials of a split without rows are written, as zeros.
+ * Alignment: h, head_w, dh and tile_sums 16-byte aligned (read and stored as whole 16-byte pieces); dheads, dw_partials,
+ * db_partials, loss_partials, gram_partials, row_index, stat_sums and gram_sums 4-byte (one element per access). */
 int brl_ppo_heads_bwd(int device, const float *dheads, const float *h, int64_t ldh, const float *head_w, int64_t batch,
                       int64_t hidden, int act, int nsplit, float *dw_partials, float *db_partials, float *dh, float *tile_sums,
                       const float *loss_partials, const float *gram_partials, int64_t ngroups, const int32_t *row_index,
@@ -417,19 +425,21 @@ int brl_ppo_heads_bwd(int device, const float *dheads, const float *h, int64_t l
 /* The log row of one step from brl_ppo_heads_loss_split's outputs (written at row *row_index when given): partials float [npartials, 8], gram_partials float [ngram, 1444] (summed
  * in order).  The illegal-action norm comes from 4 squarings of G / trace by the whole block and 16 power-iteration steps with
  * that matrix (G^256 v, as brl_ppo_stats).  total_loss includes illegal_coef * norm / 2.  row_index may be NULL (row 0).  vec_out (may be NULL): float [40] = the top right
- * singular vector v1 [38], sigma_1, 0 — what the gradient of the norm needs (d sigma_1 / dP = u1 v1^T). */
+ * singular vector v1 [38], sigma_1, 0 — what the gradient of the norm needs (d sigma_1 / dP = u1 v1^T).
+ * Every pointer 4-byte aligned (one float / int32 per access). */
 int brl_ppo_stats_gram(int device, const float *partials, int64_t npartials, int64_t batch, const float *gram_partials,
                        int64_t ngram, float vf_coef, float ent_coef, float illegal_coef, float *out_rows, const int32_t *row_index,
                        float *vec_out, void *stream);
 
 /* illegal_action_l2norm_coef != 0 (src/update.py:146-152): adds d(illegal_coef * sigma_1(P) / 2) / d(logits) to dheads float
  * [batch,39] in place — heads float [batch,39] as brl_ppo_heads_loss_split wrote them (heads_out), vec = brl_ppo_stats_gram's vec_out of
- * the same minibatch (the top right singular vector and sigma_1: d sigma_1 / dP = u1 v1^T with u1 = P v1 / sigma_1). */
+ * the same minibatch (the top right singular vector and sigma_1: d sigma_1 / dP = u1 v1^T with u1 = P v1 / sigma_1).
+ * heads, vec and dheads 4-byte aligned, mask any; column 38 of dheads (the value's gradient) is not touched. */
 int brl_ppo_illegal_grad(int device, const float *heads, const uint8_t *mask, const float *vec, float illegal_coef, int64_t batch,
                          float *dheads, void *stream);
 
 /* The log rows of `rows` minibatch steps at once (one block per row): stat_sums / gram_sums as accumulated by
- * brl_ppo_heads_bwd; out_rows float [rows,8] as brl_ppo_stats_gram writes one. */
+ * brl_ppo_heads_bwd; out_rows float [rows,8] as brl_ppo_stats_gram writes one.  stat_sums, gram_sums and out_rows 4-byte aligned. */
 int brl_ppo_stats_rows(int device, const float *stat_sums, const float *gram_sums, int64_t rows, int64_t batch, float vf_coef,
                        float ent_coef, float illegal_coef, float *out_rows, void *stream);
 
@@ -439,7 +449,11 @@ int brl_ppo_stats_rows(int device, const float *stat_sums, const float *gram_sum
  * args_dev (256 bytes, stream-ordered: a one-thread launch, no host copy) once per update; brl_mb_gather_dev(args_dev) is then a
  * launch whose parameters never change, so it lives inside the captured minibatch step and follows a new trajectory /
  * permutation.  mb_index is DEVICE memory (the Adam entry points advance it): a captured graph walks through an epoch by itself.
- * nsteps = the minibatches `perm` holds: the Adam launch's gather of a minibatch >= nsteps is skipped. */
+ * nsteps = the minibatches `perm` holds: the Adam launch's gather of a minibatch >= nsteps is skipped.
+ * Alignment: x0 16-byte aligned (an observation row is stored as 120 16-byte pieces); flat->obs 4-byte (a row is read as 120
+ * 4-byte words; 480 is a multiple of 4); perm and args_dev 8-byte (int64 / a structure of pointers); flat->action / value /
+ * log_prob, adv, targets, mb_index and the six other outputs 4-byte; both masks any; flat->done and flat->reward are not read.
+ * BRL_E_ARG otherwise (brl_mb_gather_dev: args_dev). */
 int brl_mb_gather_bind(int device, const brl_transition *flat, const float *adv, const float *targets, const int64_t *perm,
                        const int32_t *mb_index, int64_t mbs, float *x0, uint8_t *mask, int32_t *action, float *old_value,
                        float *old_log_prob, float *gae_out, float *targets_out, int64_t nsteps, void *args_dev, void *stream);
@@ -447,13 +461,16 @@ int brl_mb_gather_dev(int device, const void *args_dev, int64_t mbs, void *strea
 
 /* Backward of `h = act(z)` plus the bias gradient's partials of that layer (where brl_mlp_gemm's GATE_COLSUM epilogue does not do
  * it): dh [rows,ld] *= act'(h) in place (act 0: ReLU, 1: tanh) and the column sums of every 16-row tile into scratch float
- * [ceil(rows / 16), cols]; cols and ld multiples of 4. */
+ * [ceil(rows / 16), cols]; cols and ld multiples of 4.  dh, h and scratch 16-byte aligned (all three are moved as whole 16-byte
+ * pieces; with the multiple-of-4 ld every row then starts on one); BRL_E_ARG otherwise.  Columns >= cols of dh and h are not read. */
 int brl_act_bwd_colsum(int device, float *dh, const float *h, int64_t rows, int64_t cols, int64_t ld, int act, float *scratch,
                        void *stream);
 /* brl_act_bwd_colsum of ONE hidden layer with the weight-gradient role of brl_ppo_heads_bwd (dW_h / db_h partials + the step's
  * statistics / Gram sums; arguments as there) as extra workgroups of the same launch.  That role is not on the backward chain —
  * nothing needs its outputs before the sums at the end of the step — so it rides with a launch that is: call brl_ppo_heads_bwd
- * with dw_partials = db_partials = NULL (activation-gradient role only), then this for the first layer below the top. */
+ * with dw_partials = db_partials = NULL (activation-gradient role only), then this for the first layer below the top.
+ * Alignment: dz, hh, scratch as brl_act_bwd_colsum's (16 bytes); h 16-byte, dheads, dw_partials, db_partials, loss_partials,
+ * gram_partials, row_index, stat_sums, gram_sums 4-byte, as brl_ppo_heads_bwd's. */
 int brl_act_bwd_colsum_heads_dw(int device, float *dz, const float *hh, int64_t rows, int64_t cols, int64_t ld, int act,
                                 float *scratch, const float *dheads, const float *h, int64_t ldh, int64_t batch, int64_t hidden,
                                 int nsplit, float *dw_partials, float *db_partials, const float *loss_partials,
@@ -462,13 +479,14 @@ int brl_act_bwd_colsum_heads_dw(int device, float *dz, const float *hh, int64_t 
 
 /* The sums of several layers' tile partials in one launch: out[i][c] = sum_{t < tiles[i]} partials[i][t * cols[i] + c],
  * in order, for nseg <= 16 segments (bias gradients of the layers, and the head's weight / bias gradients from
- * brl_ppo_heads_bwd's batch splits). */
+ * brl_ppo_heads_bwd's batch splits).  Every partials[i] and out[i] 4-byte aligned (one float per load and per store; the arrays
+ * partials / cols / tiles / out themselves are host memory); BRL_E_ARG otherwise. */
 int brl_bias_finalize_ex(int device, int nseg, const float *const *partials, const int64_t *cols, const int64_t *tiles,
                          float *const *out, void *stream);
 /* The same, with the segments i >= first_row_seg written as rows of a log: out[i] + *row_index * cols[i] (row_index: device
  * memory, e.g. the minibatch counter the Adam launches advance) — the step's statistics / Gram partials summed into row
  * *row_index of stat_sums [rows,8] / gram_sums [rows,1444] (what brl_ppo_stats_rows reads) by the launch that finishes the bias
- * gradients. */
+ * gradients.  partials[i], out[i] and row_index 4-byte aligned. */
 int brl_bias_finalize_rows(int device, int nseg, const float *const *partials, const int64_t *cols, const int64_t *tiles,
                            float *const *out, int first_row_seg, const int32_t *row_index, void *stream);
 
@@ -488,8 +506,10 @@ int brl_bias_finalize_rows(int device, int nseg, const float *const *partials, c
  *         of dheads = the bias gradients' partials (brl_bias_finalize_rows: tiles = batch / 16)
  *   partials float [batch/16][8], gram_partials float [batch/16][1444] (may be NULL): the statistics as brl_ppo_heads_loss_split's.
  * net: weights in nn.Linear's [out,in] layout (w[0] [200,480], w[6] [200,680], the others [200,200]); head_w [39,200] = actor rows,
- * then the critic row; head_b [39].  act: 0 ReLU, 1 tanh.  Loss arguments as brl_ppo_heads_loss_split.  batch % 16 == 0; every
- * array 16-byte aligned. */
+ * then the critic row; head_b [39].  act: 0 ReLU, 1 tanh.  Loss arguments as brl_ppo_heads_loss_split.  batch % 16 == 0.
+ * Alignment: x0, every net->w[l] / b[l], head_w and every array of brl_fair_work 16-byte aligned (16-byte pieces, but dheads /
+ * partials / gram_partials, which are stored float by float and held to 16 bytes with the rest of the structure); head_b, action
+ * and the float columns of the loss 4-byte; mask any; BRL_E_ARG otherwise. */
 typedef struct brl_fair_net {
   const float *w[11];
   const float *b[11];
@@ -501,7 +521,8 @@ typedef struct brl_fair_work {
 } brl_fair_work;
 /* `actor(x), critic(x)` of the FAIR network alone (src/models.py:34-69 as called per env.step by src/roll_out.py:73-76 and the
  * evaluators, src/evaluation.py:52-60): x float [rows,480] -> logits float [rows,38], value float [rows], ONE launch of the same
- * kernel's forward half (16 rows per workgroup; any number of rows).  head_w = actor rows then the critic row, contiguous. */
+ * kernel's forward half (16 rows per workgroup; any number of rows).  head_w = actor rows then the critic row, contiguous.
+ * x, net->w[l] / b[l] and head_w 16-byte aligned; head_b, logits and value 4-byte (one float per access). */
 int brl_fair_forward(int device, const brl_fair_net *net, const float *x, int64_t rows, int act, float *logits, float *value,
                      void *stream);
 int brl_fair_chain(int device, const brl_fair_net *net, const float *x0, const uint8_t *mask, const int32_t *action,
@@ -518,7 +539,9 @@ int brl_fair_chain(int device, const brl_fair_net *net, const float *x0, const u
  * brl_mb_gather_bind, mbs its minibatch size; the first minibatch of an update is gathered by one brl_mb_gather_dev after the
  * bind; gather_args may be NULL).  lr_dev (may be NULL): the learning rate in device memory, used instead of `lr` (a captured
  * launch then follows ppo.py:186-192's linear schedule).  scratch: at least 1024 + sum over the segments of ceil(cols / 64)
- * floats.  norm_out (may be NULL): |g| before clipping. */
+ * floats.  norm_out (may be NULL): |g| before clipping.
+ * Alignment: p, g, m and v 16-byte aligned (the norm reads g, the sweep reads and stores all four, as whole 16-byte pieces);
+ * gather_args 8-byte; step, lr_dev, scratch, mb_index, norm_out and every partials[i] / out[i] 4-byte; BRL_E_ARG otherwise. */
 int brl_adam_clip_fin_gather(int device, float *p, float *g, float *m, float *v, int64_t n, float *step, float lr,
                              const float *lr_dev, float beta1, float beta2, float eps, float max_norm, float *scratch,
                              int64_t scratch_len, int32_t *mb_index, float *norm_out, const void *gather_args, int64_t mbs,
@@ -538,7 +561,10 @@ int brl_adam_clip_fin_gather(int device, float *p, float *g, float *m, float *v,
  *     gather_args / mbs / lr_dev / norm_out as brl_adam_clip_fin_gather.
  * Sharded form of a step: reduce-scatter per bucket, norm of the own slices, all-gather of the partials, apply on the own slices,
  * all-gather of the parameters per bucket.  Replicated form: all-reduce, norm and apply with rank_lo = 0, rank_hi = world.
- * Both give bit-identical parameters (given the same reduced gradient). */
+ * Both give bit-identical parameters (given the same reduced gradient).
+ * Alignment: p, g, m and v 16-byte aligned (with off / len multiples of 4 every slice then starts on a 16-byte piece); gather_args
+ * 8-byte; partials (exactly world * nbuckets * nsub floats), step, mb_index, lr_dev and norm_out 4-byte; BRL_E_ARG otherwise.
+ * Nothing outside the slices of ranks [rank_lo, rank_hi) is read or written in p / m / v. */
 typedef struct brl_shard_geom {
   int32_t nbuckets;   /* 1..12 */
   int32_t world;
@@ -633,7 +659,9 @@ int brl_mlp_gemm_group(int device, int layout, int count, const float *const *a,
 
 /* brl_mlp_gemm(BRL_GEMM_NN, BRL_GEMM_EPI_GATE_COLSUM, dz, w, ...) of the hidden layer below the top with the weight-gradient
  * role of brl_ppo_heads_bwd (arguments as brl_act_bwd_colsum_heads_dw) as extra workgroups of the same launch: call
- * brl_ppo_heads_bwd with dw_partials = db_partials = NULL, then this as the first product of the dz chain. */
+ * brl_ppo_heads_bwd with dw_partials = db_partials = NULL, then this as the first product of the dz chain.
+ * dz, w, out, gate and h 16-byte aligned, colsum and the role's other pointers (dheads, dw_partials, db_partials, loss_partials,
+ * gram_partials, row_index, stat_sums, gram_sums) 4-byte; BRL_E_ARG otherwise. */
 int brl_mlp_gemm_dh_heads_dw(int device, const float *dz, int64_t lddz, const float *w, int64_t ldw, float *out, int64_t ldo,
                              int64_t m, int64_t n, int64_t k, int act, const float *gate, int64_t ldg, float *colsum,
                              const float *dheads, const float *h, int64_t ldh, int64_t batch, int64_t hidden, int nsplit,

@@ -14,7 +14,8 @@ The logical elements of an OUTPUT start as a NaN / negative-integer variant of t
 ``unwritten`` tells which elements a launch never stored.  ``check`` compares every guard byte with a host mirror and names the
 nearest array, row, column and byte offset of the first difference.
 
-Also here: the ledger of which C-ABI entry points run under these guards (``COVERED``) and which do not yet (``OPEN``);
+Also here: ``Plain`` / ``Guarded`` / ``both`` — the two ways a GPU case gets its arrays, and the comparison of the two runs
+(tests/test_gpu_memory_contract.py and tests/test_gpu_memory_contract_update.py) — and the ledger of which C-ABI entry points run under these guards (``COVERED``) and which do not yet (``OPEN``);
 tests/test_guarded_host.py holds every ``int brl_*(`` declaration of include/*.h against the two.
 """
 from __future__ import annotations
@@ -193,12 +194,73 @@ class Arena:
                 raise GuardError(f"array '{self.rec(v).name}': {int(u.sum())} of {u.size} elements were never written, first {first}")
 
 
+DEV = "cuda:0"     # the device of the GPU cases' Plain tensors and Guarded arenas
+
+
+# ---- the two ways a case gets its arrays -------------------------------------------------------------------------------------
+class Plain:
+    """dense torch tensors: `ld` / `strides` are ignored, outputs start as zeros.  plain_ld: the row pitch where the dense one is not
+    a legal leading dimension (39 columns of a [., 40] array)"""
+    arena = None
+
+    def inp(self, name, values, dtype, align, ld=None, strides=None, plain_ld=None, inout=False):
+        v = torch.as_tensor(values).to(device=DEV, dtype=dtype).contiguous()
+        if plain_ld is None:
+            return v
+        wide = torch.zeros(tuple(v.shape[:-1]) + (plain_ld,), dtype=dtype, device=DEV)
+        wide[..., :v.shape[-1]] = v
+        return wide[..., :v.shape[-1]]
+
+    def out(self, name, shape, dtype, align, ld=None, strides=None, plain_ld=None):
+        if plain_ld is None:
+            return torch.zeros(shape, dtype=dtype, device=DEV)
+        return torch.zeros(tuple(shape[:-1]) + (plain_ld,), dtype=dtype, device=DEV)[..., :shape[-1]]
+
+
+class Guarded:
+    def __init__(self, capacity=1 << 22):
+        self.arena = Arena(DEV, capacity)
+        self.outs = {}
+
+    def inp(self, name, values, dtype, align, ld=None, strides=None, plain_ld=None, inout=False):
+        """inout: the launch may change its elements (a state updated in place, a counter, a workspace); any other input must
+        still hold its values afterwards"""
+        v = torch.as_tensor(values)
+        return self.arena.place(tuple(v.shape), dtype, align, ld=ld, strides=strides, fill=v, name=name, inout=inout)
+
+    def out(self, name, shape, dtype, align, ld=None, strides=None, plain_ld=None):
+        self.outs[name] = self.arena.place(shape, dtype, align, ld=ld, strides=strides, name=name)
+        return self.outs[name]
+
+
+def _bits(t):
+    t = t.detach().contiguous().cpu()
+    return t.reshape(-1).view(torch.uint8) if t.numel() else t.reshape(-1)
+
+
+def both(run, capacity=1 << 22, allowed=(), partial=()):
+    """run(mem) -> {name: tensor} on Plain and on Guarded memory: the same bits, no guard byte changed, every element of every
+    output written (but those named in `partial`, which the caller checks itself).  allowed: names -> (col_lo, col_hi) of
+    padding columns the header lets the kernel write.  -> (plain results, guarded results, Guarded)"""
+    p = run(Plain())
+    gm = Guarded(capacity)
+    g = run(gm)
+    cur = gm.arena.check(allowed=[(gm.outs[name], lo, hi) for name, (lo, hi) in dict(allowed).items()])
+    assert set(p) == set(g)
+    for name in p:
+        assert p[name].shape == g[name].shape, name
+        assert torch.equal(_bits(p[name]), _bits(g[name])), f"{name}: the guarded result differs from the plain one"
+    gm.arena.assert_written(*[v for name, v in gm.outs.items() if name not in partial], cur=cur)
+    return p, g, gm
+
+
 def round_up(x: int, q: int) -> int:
     return (x + q - 1) // q * q
 
 
 # ---- the ledger: every `int brl_*(` of include/*.h is in exactly one of the two ------------------------------------------------
-# COVERED: entry point -> what tests/test_gpu_memory_contract.py runs it on (alignments, strides, shapes)
+# COVERED: entry point -> what tests/test_gpu_memory_contract.py (the PPO step's own entry points: tests/test_gpu_memory_contract_update.py)
+# runs it on (alignments, strides, shapes)
 COVERED = {
     "brl_mlp_gemm": "a / b / c / bias / gate at 16 bytes, colsum / sqsum at 4 and exactly sized; lda / ldb / ldc / ldg = dense + 4; NT, NN, TN x "
                     "every epilogue at (4,4,4), (68,36,52), (60,132,8); 64 x 32 tiles, and 64 x 64 in a child process (BRL_GEMM_TILE_N=64)",
@@ -236,6 +298,35 @@ COVERED = {
     "brl_distill_targets": "B in {1, 65}, K = 2; rows of 40 floats (NaN padding, teachers 4 floats further apart than dense) and the [K, n, 39] "
                            "heads; floats at 4, mask at 1",
     "brl_distill_loss": "as brl_distill_targets; u at stride 2; work at 8, exactly 8 doubles per block of 64 rows; dz / du given and NULL",
+    "brl_ppo_loss": "batch in {1, 5, 67}; logits_stride 38 / 40 (NaN in columns 38, 39); masked and unmasked; illegal_probs given and NULL; "
+                    "partials exactly ceil(batch / 4) * 8 floats; floats / int32 at 4, mask at 1",
+    "brl_ppo_stats": "on those partials; gram given and NULL; everything at 4",
+    "brl_ppo_heads_loss_split": "hidden in {16, 272}, ldh = hidden + 4, batch in {1, 5, 67}, ksplit 1 and 8, head_parts exactly [ksplit, batch, 39]; "
+                                "heads_out / gram_partials given and NULL; reward_scaling 0 and 1; h / head_w at 16, the rest at 4",
+    "brl_ppo_stats_gram": "on the partials of brl_ppo_heads_loss_split; row_index NULL, and row 2 of 4 (the other rows untouched); vec_out given and NULL",
+    "brl_ppo_stats_rows": "rows in {1, 3}; stat_sums / gram_sums / out_rows exactly sized, at 4",
+    "brl_ppo_illegal_grad": "batch in {1, 5, 67}; dheads in/out, column 38 keeps its bits; everything at 4, mask at 1",
+    "brl_ppo_heads_bwd": "hidden 256, ldh = 260, batch in {1, 17, 65}, nsplit = ceil(batch / 64) and one more; with the sums (row 2 of 4), without, "
+                         "and dw_partials = db_partials = NULL; h / head_w / dh / tile_sums at 16, tile_sums exactly ceil(batch / 16) * 256",
+    "brl_mb_gather_bind": "a trajectory of 12 rows, every brl_transition column its own placement (obs at 4), mbs in {1, 5}, *mb_index 0 and the "
+                          "last; perm / args_dev (256 bytes) at 8, x0 at 16, the seven outputs exactly sized",
+    "brl_mb_gather_dev": "as brl_mb_gather_bind: the launch that reads args_dev",
+    "brl_act_bwd_colsum": "rows in {1, 17, 65} x cols in {4, 260}, ld = cols + 4 (NaN padding in dh and h), both activations; dh / h / scratch at 16, "
+                          "scratch exactly ceil(rows / 16) * cols",
+    "brl_act_bwd_colsum_heads_dw": "(rows, cols) in {(1,4), (17,260), (65,4), (65,260)} + the heads' dW role at hidden 256, batch in {17, 65}, nsplit "
+                                   "ceil(batch / 64) and one more, with and without the sums; every output of the role exactly sized",
+    "brl_bias_finalize_ex": "three segments in one launch, cols (39, 4, 260), tiles (1, 3, 5); partials exactly tiles * cols, at 4",
+    "brl_bias_finalize_rows": "the same segments; first_row_seg in {0, 1, 3}, row_index = 2 of 4 rows (the other rows untouched)",
+    "brl_adam_clip_fin_gather": "n in {8, 4100}; segments (4) and (4, 39 + 1 pad) tiling the end of g; scratch exactly 1024 + sum ceil(cols / 64); lr_dev / "
+                                "norm_out / mb_index / gather_args (bound to the 12-row trajectory) given and NULL; max_norm 0.5 and 0; p / g / m / v at 16",
+    "brl_adam_shard_norm": "world 2, two buckets 4 floats apart and 4 in front of the end, len in {4, 1028}, nsub in {1, 3}, ranks [0,1), [1,2), [0,2); "
+                           "partials exactly world * nbuckets * nsub: only the range's rows written",
+    "brl_adam_shard_apply": "the same geometry: gap, tail and the other ranks' slices keep their bits in p / m / v; g read only; p / g / m / v at 16",
+    "brl_mlp_gemm_dh_heads_dw": "NN + GATE_COLSUM at (m, n, k) = (batch, 36, 52), every ld + 4, with the heads' dW role at hidden 256, batch in {17, 65}, "
+                                "with and without the sums; dz / w / out / gate / h at 16",
+    "brl_fair_forward": "rows in {1, 17}; x and the weights at 16, head_b / logits [rows, 38] / value [rows] at 4 and exactly sized",
+    "brl_fair_chain": "batch in {16, 48}; every brl_fair_work array its own placement at 16, exactly the header's size; gram_partials given and NULL; "
+                      "both activations",
 }
 
 _NOT_YET = "not yet placed in an arena: "
@@ -249,15 +340,10 @@ OPEN = {
     "brl_set_rng": "no arrays",
 }
 for _n, _why in {
-    "brl_mlp_gemm_dh_heads_dw": "brl_mlp_gemm's tile code (guarded there) + the heads' dW role, which needs the step's 256-multiple hidden sizes",
     "brl_policy_step": "brl_policy_step_ex with dense logits and no ext block (the same kernel, guarded there)",
     "brl_policy_step_at": "brl_policy_step_ex without the ext block (the same kernel, guarded there)",
     "brl_init_from_deals": "", "brl_get_fields": "", "brl_imp_reward": "", "brl_duplicate_step": "",
     "brl_eval_step": "", "brl_eval_step_team": "", "brl_eval_reduce": "",
-    "brl_ppo_loss": "", "brl_ppo_stats": "", "brl_ppo_heads_loss_split": "", "brl_ppo_heads_bwd": "", "brl_ppo_stats_gram": "",
-    "brl_ppo_illegal_grad": "", "brl_ppo_stats_rows": "", "brl_mb_gather_bind": "", "brl_mb_gather_dev": "",
-    "brl_act_bwd_colsum": "", "brl_act_bwd_colsum_heads_dw": "", "brl_bias_finalize_ex": "", "brl_bias_finalize_rows": "",
-    "brl_fair_forward": "", "brl_fair_chain": "", "brl_adam_clip_fin_gather": "", "brl_adam_shard_norm": "", "brl_adam_shard_apply": "",
     "brl_league_route": "", "brl_league_forward": "", "brl_board_records": "", "brl_board_imp": "", "brl_board_keep_a": "",
     "brl_book_samples": "", "brl_book_reduce": "", "brl_par": "", "brl_par_imp": "", "brl_review_expand": "", "brl_review_reduce": "",
     "brl_belief_deal": "", "brl_belief_logp": "", "brl_belief_reduce": "", "brl_belief_resample": "", "brl_belief_propose": "",

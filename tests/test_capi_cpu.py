@@ -184,6 +184,122 @@ def test_handle_entry_points_refuse_misaligned_pointers_before_anything_else(bui
     assert pol(ctypes.byref(_capi.MacroExt(obs_cast=P))) == -1 and b"handle" in L.brl_last_error()
 
 
+def test_update_entry_points_refuse_misaligned_pointers_before_anything_else(built_lib):
+    """The PPO step's entry points (include/brl_hip.h states the alignment of every pointer argument): each pointer in turn is
+    moved to half its alignment — 16-byte ones to P + 8, 8-byte ones to P + 4, 4-byte ones to P + 2 — and the call must come back
+    with BRL_E_ARG and a message that names the argument; the pointers inside brl_transition, brl_fair_net, brl_fair_work and the
+    finalize segments' partials[i] / out[i] too.  The checks stand in front of everything else, so made-up addresses and a
+    device that does not exist are enough: nothing is read, nothing is launched.  With every pointer aligned the same call gets
+    past them (whatever stops it then does not speak of alignment)."""
+    from brl_amd import _capi
+    L = _capi.lib()
+    P, DEV = 0x7F0000000000, 1 << 20
+    vp2, i64x2 = ctypes.c_void_p * 2, ctypes.c_int64 * 2
+
+    def ask(fn, args, needs):
+        """needs: {index in args: (alignment, words of the refusal)}"""
+        rc = getattr(L, fn)(*args)
+        assert rc != 0 and b"aligned" not in L.brl_last_error(), (fn, rc, L.brl_last_error())
+        for i, (align, what) in needs.items():
+            bad = list(args)
+            bad[i] = P + align // 2
+            assert getattr(L, fn)(*bad) == -1, (fn, i)
+            err = L.brl_last_error()
+            assert what in err and b"aligned" in err, (fn, i, err)
+
+    f4 = lambda idx, what: {i: (4, what) for i in idx}          # noqa: E731
+    f16 = lambda idx, what: {i: (16, what) for i in idx}        # noqa: E731
+    ask("brl_ppo_loss", [DEV, P, 40, P, P + 1, P, P, P, P, P, 5, 0.2, 0.5, 0.01, 1, 1, P, P, P, P, None],
+        f4((1, 3, 5, 6, 7, 8, 9, 16, 17, 18, 19), b"logits / value"))
+    ask("brl_ppo_stats", [DEV, P, 5, P, 0.5, 0.01, P, None], f4((1, 3, 6), b"partials / gram / out"))
+    ask("brl_ppo_heads_loss_split", [DEV, P, 20, P, P, 16, P + 1, P, P, P, P, P, 5, 0.2, 0.5, 0.01, 1, 1, 0, P, P, P, P, P, 1, None],
+        {**f16((1, 3), b"h / head_w"), **f4((4, 7, 8, 9, 10, 11, 19, 20, 21, 22, 23), b"head_b / action")})
+    ask("brl_ppo_heads_bwd", [DEV, P, P, 260, P, 5, 256, 0, 1, P, P, P, P, P, P, 2, P, P, P, None],
+        {**f16((2, 4, 11, 12), b"h / head_w / dh / tile_sums"), **f4((1, 9, 10, 13, 14, 16, 17, 18), b"dheads / dw_partials")})
+    ask("brl_ppo_stats_gram", [DEV, P, 2, 5, P, 2, 0.5, 0.01, 0.0, P, P, P, None], f4((1, 4, 9, 10, 11), b"partials / gram_partials / out_rows"))
+    ask("brl_ppo_illegal_grad", [DEV, P, P + 1, P, 0.1, 5, P, None], f4((1, 3, 6), b"heads / vec / dheads"))
+    ask("brl_ppo_stats_rows", [DEV, P, P, 3, 5, 0.5, 0.01, 0.0, P, None], f4((1, 2, 8), b"stat_sums / gram_sums / out_rows"))
+    ask("brl_act_bwd_colsum", [DEV, P, P, 5, 8, 12, 0, P, None], f16((1, 2, 7), b"dh / h / scratch"))
+    ask("brl_act_bwd_colsum_heads_dw", [DEV, P, P, 5, 256, 260, 0, P, P, P, 260, 5, 256, 1, P, P, P, P, 2, P, P, P, None],
+        {**f16((1, 2, 7, 9), b"dz / hh / scratch / h"), **f4((8, 14, 15, 16, 17, 19, 20, 21), b"dheads / dw_partials")})
+    ask("brl_mlp_gemm_dh_heads_dw", [DEV, P, 256, P, 256, P, 256, 64, 256, 256, 0, P, 256, P, P, P, 256, 64, 256, 1, P, P, P, P, 16, P, P, P,
+                                     None],
+        {15: (16, b"h not 16-byte"), **f4((14, 20, 21, 22, 23, 25, 26, 27), b"dheads / dw_partials")})
+    ask("brl_mb_gather_dev", [DEV, P, 5, None], {1: (8, b"args_dev")})
+
+    # brl_mb_gather_bind: the trajectory's columns, then its own arguments
+    def bind(tp, *rest):
+        return L.brl_mb_gather_bind(DEV, ctypes.byref(tp), *rest)
+    rest = [P, P, P, P, 5, P, P + 1, P, P, P, P, P, 2, P, None]
+    for name in _capi.TransitionPtrs._names:
+        tp = _capi.TransitionPtrs(**{n: P for n in _capi.TransitionPtrs._names})
+        setattr(tp, name, P + (1 if name in ("legal_action_mask", "done") else 2))
+        rc = bind(tp, *rest)
+        if name in ("legal_action_mask", "done", "reward"):      # bytes, and two columns the gather does not read
+            assert b"aligned" not in L.brl_last_error(), name
+        else:
+            assert rc == -1 and b"trajectory" in L.brl_last_error() and b"aligned" in L.brl_last_error(), name
+    tp = _capi.TransitionPtrs(**{n: P for n in _capi.TransitionPtrs._names})
+    for i, (align, what) in {**f4((0, 1, 3, 7, 8, 9, 10, 11), b"adv / targets / mb_index"), 2: (8, b"perm, args_dev"), 5: (16, b"x0"),
+                             13: (8, b"perm, args_dev")}.items():
+        bad = list(rest)
+        bad[i] = P + align // 2
+        assert bind(tp, *bad) == -1 and what in L.brl_last_error() and b"aligned" in L.brl_last_error(), i
+    assert bind(tp, *rest) != 0 and b"aligned" not in L.brl_last_error()
+
+    # the finalize segments: partials[i] / out[i] of the SECOND segment
+    cols, tiles = i64x2(4, 4), i64x2(1, 1)
+    for which in (0, 1):
+        ptrs = [vp2(P, P + 2) if j == which else vp2(P, P) for j in range(2)]
+        assert L.brl_bias_finalize_ex(DEV, 2, ptrs[0], cols, tiles, ptrs[1], None) == -1 and b"partials[i] / out[i]" in L.brl_last_error()
+        assert L.brl_bias_finalize_rows(DEV, 2, ptrs[0], cols, tiles, ptrs[1], 1, P, None) == -1 and b"partials[i] / out[i]" in L.brl_last_error()
+        assert L.brl_adam_clip_fin_gather(DEV, P, P, P, P, 8, P, 1e-3, P, 0.9, 0.999, 1e-8, 0.5, P, 2048, P, P, P, 5, 2, ptrs[0], cols,
+                                          tiles, ptrs[1], None) == -1 and b"partials[i] / out[i]" in L.brl_last_error()
+    ok = vp2(P, P)
+    assert L.brl_bias_finalize_rows(DEV, 2, ok, cols, tiles, ok, 1, P + 2, None) == -1 and b"row_index" in L.brl_last_error()
+    assert L.brl_bias_finalize_ex(DEV, 2, ok, cols, tiles, ok, None) != 0 and b"aligned" not in L.brl_last_error()
+    assert L.brl_bias_finalize_rows(DEV, 2, ok, cols, tiles, ok, 1, P, None) != 0 and b"aligned" not in L.brl_last_error()
+    ask("brl_adam_clip_fin_gather", [DEV, P, P, P, P, 8, P, 1e-3, P, 0.9, 0.999, 1e-8, 0.5, P, 2048, P, P, P, 5, 2, ok, cols, tiles, ok, None],
+        {**f16((1, 2, 3, 4), b"p / g / m / v"), 17: (8, b"gather_args"), **f4((6, 8, 13, 15, 16), b"step / lr_dev / scratch")})
+    geom = _capi.ShardGeom()
+    geom.nbuckets, geom.world, geom.nsub = 1, 1, 1
+    geom.off[0], geom.len[0] = 0, 8
+    ask("brl_adam_shard_norm", [DEV, P, ctypes.byref(geom), 0, 1, 1.0, P, P, P, None],
+        {1: (16, b"g not 16-byte"), **f4((6, 7, 8), b"partials, step, mb_index")})
+    ask("brl_adam_shard_apply", [DEV, P, P, P, P, ctypes.byref(geom), 0, 1, P, P, 1e-3, P, 0.9, 0.999, 1e-8, 0.5, 1.0, P, P, 5, None],
+        {**f16((1, 2, 3, 4), b"p / g / m / v"), 18: (8, b"gather_args"), **f4((8, 9, 11, 17), b"partials / step / lr_dev / norm_out")})
+
+    # the FAIR entry points: the structures' pointers, then their own
+    def fair_net(**k):
+        net = _capi.FairNet()
+        for l in range(11):
+            net.w[l], net.b[l] = P, P
+        net.head_w, net.head_b = k.get("head_w", P), k.get("head_b", P)
+        if "w" in k:
+            net.w[10] = k["w"]
+        if "b" in k:
+            net.b[10] = k["b"]
+        return ctypes.byref(net)
+
+    def fair_work(**k):
+        return ctypes.byref(_capi.FairWork(**{n: k.get(n, P) for n in _capi.FairWork._names}))
+    chain = lambda net=None, work=None, x0=P, cols=(P,) * 5: L.brl_fair_chain(   # noqa: E731
+        DEV, net or fair_net(), x0, P + 1, *cols, 16, 0.2, 0.5, 0.01, 1, 1, 0, 0, work or fair_work(), None)
+    fwd = lambda net=None, x=P, logits=P, value=P: L.brl_fair_forward(DEV, net or fair_net(), x, 3, 0, logits, value, None)   # noqa: E731
+    for call in (chain, fwd):
+        for kw in (dict(w=P + 8), dict(b=P + 8), dict(head_w=P + 8), dict(head_b=P + 2)):
+            assert call(net=fair_net(**kw)) == -1 and b"net" in L.brl_last_error() and b"align" in L.brl_last_error(), kw
+        assert call() != 0 and b"aligned" not in L.brl_last_error()
+    for name in _capi.FairWork._names:
+        assert chain(work=fair_work(**{name: P + 8})) == -1 and b"16-byte align" in L.brl_last_error(), name
+    assert chain(x0=P + 8) == -1 and b"16-byte align" in L.brl_last_error()
+    for i in range(5):
+        assert chain(cols=tuple(P + 2 if j == i else P for j in range(5))) == -1 and b"action / old_value" in L.brl_last_error(), i
+    assert fwd(x=P + 8) == -1 and b"x: 16-byte" in L.brl_last_error()
+    assert fwd(logits=P + 2) == -1 and b"logits / value" in L.brl_last_error()
+    assert fwd(value=P + 2) == -1 and b"logits / value" in L.brl_last_error()
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     import brl_amd

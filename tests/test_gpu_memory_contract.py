@@ -21,7 +21,7 @@ import pytest
 import torch
 
 from tests import distill_ref, sl_teacher
-from tests.guarded import Arena, round_up
+from tests.guarded import Arena, Guarded, Plain, _bits, both, round_up  # noqa: F401
 from tests.gpu_util import gemm_bound, gemm_operands, gemm_ref64, make_env
 from tests.nets import forward64, raw_net
 
@@ -30,63 +30,6 @@ DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, BF16, F16, U8, I16, I32, I64 = (torch.float32, torch.bfloat16, torch.float16, torch.uint8, torch.int16, torch.int32,
                                      torch.int64)
-
-
-# ---- the two ways a case gets its arrays -------------------------------------------------------------------------------------
-class Plain:
-    """dense torch tensors: `ld` / `strides` are ignored, outputs start as zeros.  plain_ld: the row pitch where the dense one is not
-    a legal leading dimension (39 columns of a [., 40] array)"""
-    arena = None
-
-    def inp(self, name, values, dtype, align, ld=None, strides=None, plain_ld=None, inout=False):
-        v = torch.as_tensor(values).to(device=DEV, dtype=dtype).contiguous()
-        if plain_ld is None:
-            return v
-        wide = torch.zeros(tuple(v.shape[:-1]) + (plain_ld,), dtype=dtype, device=DEV)
-        wide[..., :v.shape[-1]] = v
-        return wide[..., :v.shape[-1]]
-
-    def out(self, name, shape, dtype, align, ld=None, strides=None, plain_ld=None):
-        if plain_ld is None:
-            return torch.zeros(shape, dtype=dtype, device=DEV)
-        return torch.zeros(tuple(shape[:-1]) + (plain_ld,), dtype=dtype, device=DEV)[..., :shape[-1]]
-
-
-class Guarded:
-    def __init__(self, capacity=1 << 22):
-        self.arena = Arena(DEV, capacity)
-        self.outs = {}
-
-    def inp(self, name, values, dtype, align, ld=None, strides=None, plain_ld=None, inout=False):
-        """inout: the launch may change its elements (a state updated in place, a counter, a workspace); any other input must
-        still hold its values afterwards"""
-        v = torch.as_tensor(values)
-        return self.arena.place(tuple(v.shape), dtype, align, ld=ld, strides=strides, fill=v, name=name, inout=inout)
-
-    def out(self, name, shape, dtype, align, ld=None, strides=None, plain_ld=None):
-        self.outs[name] = self.arena.place(shape, dtype, align, ld=ld, strides=strides, name=name)
-        return self.outs[name]
-
-
-def _bits(t):
-    t = t.detach().contiguous().cpu()
-    return t.reshape(-1).view(torch.uint8) if t.numel() else t.reshape(-1)
-
-
-def both(run, capacity=1 << 22, allowed=(), partial=()):
-    """run(mem) -> {name: tensor} on Plain and on Guarded memory: the same bits, no guard byte changed, every element of every
-    output written (but those named in `partial`, which the caller checks itself).  allowed: names -> (col_lo, col_hi) of
-    padding columns the header lets the kernel write.  -> (plain results, guarded results, Guarded)"""
-    p = run(Plain())
-    gm = Guarded(capacity)
-    g = run(gm)
-    cur = gm.arena.check(allowed=[(gm.outs[name], lo, hi) for name, (lo, hi) in dict(allowed).items()])
-    assert set(p) == set(g)
-    for name in p:
-        assert p[name].shape == g[name].shape, name
-        assert torch.equal(_bits(p[name]), _bits(g[name])), f"{name}: the guarded result differs from the plain one"
-    gm.arena.assert_written(*[v for name, v in gm.outs.items() if name not in partial], cur=cur)
-    return p, g, gm
 
 
 def _s():
