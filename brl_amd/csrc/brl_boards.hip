@@ -207,6 +207,7 @@ extern "C" int brl_board_imp(int device, const brl_board_record *records_a, cons
                              int32_t *out_imp, void *stream) {
   NEED(records_a && records_b && out_imp, "NULL array");
   NEED(n > 0 && n < ((int64_t)1 << 31), "n (1 .. 2^31)");
+  NEED(((((uintptr_t)records_a) | ((uintptr_t)records_b)) & 7) == 0 && (((uintptr_t)out_imp) & 3) == 0, "records 8-byte aligned, out_imp 4-byte");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_board_imp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, records_a, records_b, n, out_imp);
   HIP_TRY(hipGetLastError());
@@ -217,7 +218,8 @@ extern "C" int brl_board_keep_a(int device, const uint64_t *state, uint64_t *pre
                                 uint8_t *taken, uint64_t *final_a, int64_t n, void *stream) {
   NEED(state && prev && action && a_done && taken && final_a, "NULL array");
   NEED(n > 0 && n < ((int64_t)1 << 31), "n (1 .. 2^31)");
-  NEED(((((uintptr_t)state) | ((uintptr_t)prev) | ((uintptr_t)final_a)) & 15) == 0, "state / prev / final_a 16-byte aligned");
+  NEED(((((uintptr_t)state) | ((uintptr_t)prev) | ((uintptr_t)final_a)) & 15) == 0 && (((uintptr_t)action) & 3) == 0,
+       "state / prev / final_a 16-byte aligned, action 4-byte");
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_board_keep_a, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, state, prev, action, a_done,
                      taken, final_a, n);

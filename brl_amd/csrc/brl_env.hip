@@ -337,6 +337,8 @@ extern "C" int brl_init_random(brl_handle *h, uint64_t *state, int64_t n, uint32
 extern "C" int brl_init_from_deals(brl_handle *h, uint64_t *state, int64_t n, const int32_t *hand,
                                    const int32_t *dealer, const uint8_t *vul_ns, const uint8_t *vul_ew,
                                    const int32_t *shuffled_players, const uint8_t *tricks, void *stream) {
+  NEED(ptr_aligned(state, 8) && ptr_aligned(hand, 4) && ptr_aligned(dealer, 4) && ptr_aligned(shuffled_players, 4),
+       "state not 8-byte aligned, int32 arrays not 4-byte");
   COMMON(h, n);
   NEED(state && hand && dealer && vul_ns && vul_ew && shuffled_players && tricks, "NULL input array");
   hipLaunchKernelGGL(k_init_explicit, dim3(thread_grid(n, 128)), dim3(128), 0, (hipStream_t)stream, state, n, hand,
@@ -366,7 +368,17 @@ extern "C" int brl_observe(brl_handle *h, const uint64_t *state, int64_t n, cons
   return BRL_OK;
 }
 
+// every int32 / uint32 member of brl_fields (all but the uint8 ones and rewards)
+static bool fields_aligned(const brl_fields *f) {
+  const void *i32[] = {f->current_player, f->step_count, f->turn, f->dealer, f->shuffled_players, f->last_bid, f->last_bidder, f->pass_num,
+                       f->first_denomination_ns, f->first_denomination_ew, f->hand, f->lut_idx, f->board_ctr};
+  for (const void *p : i32)
+    if (!ptr_aligned(p, 4)) return false;
+  return ptr_aligned(f->rewards, 16);   // a table's four rewards are ONE 16-byte store (k_get_fields)
+}
+
 extern "C" int brl_get_fields(brl_handle *h, const uint64_t *state, int64_t n, const brl_fields *out, void *stream) {
+  NEED(ptr_aligned(state, 8) && (out == nullptr || fields_aligned(out)), "state not 8-byte aligned, rewards not 16-byte, int32 members not 4-byte");
   COMMON(h, n);
   NEED(state && out, "state / out");
   hipLaunchKernelGGL(k_get_fields, dim3(thread_grid(n, 128)), dim3(128), 0, (hipStream_t)stream, state, n, *out);
@@ -386,6 +398,8 @@ extern "C" int brl_gae(brl_handle *h, const uint8_t *done, const float *value, c
 }
 
 extern "C" int brl_imp_reward(brl_handle *h, const float *a, const float *b, float *out, int64_t n, void *stream) {
+  // a board's IMP vector is ONE 16-byte store; of a and b only the first float of a row is read
+  NEED(ptr_aligned(a, 4) && ptr_aligned(b, 4) && ptr_aligned(out, 16), "out not 16-byte aligned, a / b not 4-byte");
   COMMON(h, n);
   NEED(a && b && out, "NULL array");
   hipLaunchKernelGGL(k_imp_reward, dim3(thread_grid(n, 128)), dim3(128), 0, (hipStream_t)stream, a, b, out, n);

@@ -277,6 +277,17 @@ static bool table_info_ok(const brl_table_info *t) {
   return t && t->terminated && t->rewards && t->last_bid && t->last_bidder && t->call_x && t->call_xx;
 }
 
+// What k_eval_step asks of the evaluators' own arrays (include/brl_hip.h, brl_eval_step): rewards_sum is updated as ONE 16-byte
+// piece per board, everything else as its element type.  stats may be NULL, and so may every pointer.
+static bool eval_arrays_aligned(const float *logits1, const float *logits2, const brl_eval_stats *s, const float *cum_return,
+                                const float *rewards_sum, const int32_t *action_out) {
+  if (s && !(ptr_aligned(s->illegal_prob_sum, 4) && ptr_aligned(s->step_count, 4) && ptr_aligned(s->pass_count, 4) && ptr_aligned(s->bid_count, 4)))
+    return false;
+  return ptr_aligned(logits1, 4) && ptr_aligned(logits2, 4) && ptr_aligned(cum_return, 4) && ptr_aligned(rewards_sum, 16) &&
+         ptr_aligned(action_out, 4);
+}
+#define EVAL_ALIGN_MSG "rewards_sum not 16-byte aligned, logits / stats / cum_return / action_out not 4-byte"
+
 static int eval_step_impl(brl_handle *h, EvalArgs &A, void *stream) {
   LAUNCH_K(h, k_eval_step, A.n, stream, A);
   return BRL_OK;
@@ -286,6 +297,8 @@ extern "C" int brl_duplicate_step(brl_handle *h, const uint64_t *state_in, uint6
                                   const int32_t *action, const brl_table_info *table_a,
                                   const brl_table_info *table_b, uint8_t *obs, uint8_t *mask, float *rewards,
                                   uint8_t *terminated, int32_t *current_player, void *stream) {
+  NEED(step_outputs_aligned(state_in, state_out, obs, rewards, action, current_player), STEP_ALIGN_MSG);
+  NEED(table_info_aligned(table_a) && table_info_aligned(table_b), TABLE_ALIGN_MSG);
   COMMON(h, n);
   NEED(state_in && state_out && action, "NULL state / action");
   NEED(table_info_ok(table_a) && table_info_ok(table_b), "table_a / table_b has NULL members");
@@ -302,6 +315,9 @@ extern "C" int brl_eval_step(brl_handle *h, const uint64_t *state_in, uint64_t *
                              const brl_table_info *table_a, const brl_table_info *table_b, const brl_eval_stats *stats,
                              int bid_set, float *cum_return, float *rewards_sum, int32_t *action_out, uint8_t *obs,
                              uint8_t *mask, float *rewards, uint8_t *terminated, int32_t *current_player, void *stream) {
+  NEED(step_outputs_aligned(state_in, state_out, obs, rewards, nullptr, current_player), STEP_ALIGN_MSG);
+  NEED(table_info_aligned(table_a) && table_info_aligned(table_b), TABLE_ALIGN_MSG);
+  NEED(eval_arrays_aligned(logits_team1, logits_team2, stats, cum_return, rewards_sum, action_out), EVAL_ALIGN_MSG);
   COMMON(h, n);
   NEED(state_in && state_out && logits_team1 && logits_team2, "NULL state / logits");
   NEED(stride1 >= BRL_NUM_ACTIONS && stride2 >= BRL_NUM_ACTIONS, "logits stride");
@@ -324,11 +340,14 @@ extern "C" int brl_eval_step_team(brl_handle *h, const uint64_t *state_in, uint6
                                   const brl_table_info *table_b, const brl_eval_stats *stats, int bid_set, float *cum_return,
                                   float *rewards_sum, int32_t *action_out, uint8_t *obs, uint8_t *mask, float *rewards,
                                   uint8_t *terminated, int32_t *current_player, float *obs_f32, void *stream) {
+  NEED(step_outputs_aligned(state_in, state_out, obs, rewards, nullptr, current_player), STEP_ALIGN_MSG);
+  NEED(table_info_aligned(table_a) && table_info_aligned(table_b), TABLE_ALIGN_MSG);
+  NEED(eval_arrays_aligned(logits, nullptr, stats, cum_return, rewards_sum, action_out), EVAL_ALIGN_MSG);
+  NEED((((uintptr_t)obs_f32) & 15) == 0, "obs_f32 not 16-byte aligned");
   COMMON(h, n);
   NEED(state_in && state_out && logits, "NULL state / logits");
   NEED(stride >= BRL_NUM_ACTIONS, "logits stride");
   NEED(acting_team == 0 || acting_team == 1, "acting_team");
-  NEED((((uintptr_t)obs_f32) & 15) == 0, "obs_f32 not 16-byte aligned");
   NEED((table_a == nullptr) == (table_b == nullptr), "table_a and table_b go together");
   if (table_a) NEED(table_info_ok(table_a) && table_info_ok(table_b), "table_a / table_b has NULL members");
   EvalArgs A{};
@@ -346,6 +365,9 @@ extern "C" int brl_eval_step_team(brl_handle *h, const uint64_t *state_in, uint6
 
 extern "C" int brl_eval_reduce(brl_handle *h, int64_t n, const brl_table_info *table_a, const brl_table_info *table_b,
                                const int32_t *bid_count, const uint64_t *state, int64_t *out, void *stream) {
+  // a board's 70 bid counters are read as 35 8-byte pairs (70 * 4 bytes per board keeps every board's first pair 8-byte aligned)
+  NEED(ptr_aligned(bid_count, 8) && ptr_aligned(state, 8) && ptr_aligned(out, 8), "bid_count / state / out not 8-byte aligned");
+  NEED(table_info_aligned(table_a) && table_info_aligned(table_b), TABLE_ALIGN_MSG);
   COMMON(h, n);
   NEED(table_info_ok(table_a) && out, "table_a / out");
   if (table_b) NEED(table_info_ok(table_b), "table_b has NULL members");

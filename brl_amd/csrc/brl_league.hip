@@ -159,6 +159,10 @@ extern "C" int brl_league_forward(int device, const brl_league_net *nets, int64_
   NEED(act == 0 || act == 1, "act (0 ReLU, 1 tanh)");
   NEED(ldo >= NHEADS, "ldo (>= 39)");
   NEED(scratch_len >= rmax * (BRL_OBS_SIZE + 2 * hidden) && (((uintptr_t)scratch) & 15) == 0, "scratch: rmax * (480 + 2 * hidden) floats, 16-byte aligned");
+  // (the cast reads an observation row as 4-byte words, as brl_mlp_forward_rows does; the arrays the records of `nets` name live on
+  //  the device and cannot be checked here)
+  NEED((((uintptr_t)obs | (uintptr_t)group_first | (uintptr_t)out) & 3) == 0 && ((((uintptr_t)rows) | ((uintptr_t)nets)) & 7) == 0,
+       "obs / group_first / out not 4-byte aligned (rows, nets: 8-byte)");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int G = (int)ngroups, H = (int)hidden;

@@ -50,6 +50,13 @@ static inline bool step_outputs_aligned(const void *state_in, const void *state_
 }
 #define STEP_ALIGN_MSG "state / obs not 8-byte aligned, rewards not 16-byte, int32 / float columns not 4-byte"
 
+// brl_table_info as the evaluators' step moves it (k_eval_step): a board's four rewards leave — and, on the step table B ends,
+// come back — as ONE 16-byte piece; last_bid / last_bidder as their element type.  t may be NULL (the single-table form).
+static inline bool table_info_aligned(const brl_table_info *t) {
+  return t == nullptr || (ptr_aligned(t->rewards, 16) && ptr_aligned(t->last_bid, 4) && ptr_aligned(t->last_bidder, 4));
+}
+#define TABLE_ALIGN_MSG "table_a / table_b: rewards not 16-byte aligned, last_bid / last_bidder not 4-byte"
+
 #define COMMON(h, n)                 \
   NEED((h) != nullptr, "handle");    \
   NEED((n) >= 0, "n");               \

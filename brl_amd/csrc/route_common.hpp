@@ -64,6 +64,8 @@ inline int check_args(const uint8_t *terminated, const int32_t *current_player, 
                       const int32_t *group_of, int64_t nmatch, int64_t ngroups, const int32_t *work, const int64_t *rows,
                       const int32_t *group_first) {
   NEED(terminated && current_player && order && group_of && work && rows && group_first, "NULL array");
+  NEED((((uintptr_t)current_player | (uintptr_t)order | (uintptr_t)group_of | (uintptr_t)work | (uintptr_t)group_first) & 3) == 0 &&
+           (((uintptr_t)rows) & 7) == 0, "int32 arrays not 4-byte aligned, rows not 8-byte");
   NEED(team == 0 || team == 1, "team (0 / 1)");
   NEED(n > 0 && nmatch > 0 && ngroups > 0, "n / nmatch / ngroups");
   NEED(nmatch * n < ((int64_t)1 << 31) && nmatch < ((int64_t)1 << 24) && ngroups < ((int64_t)1 << 24), "nmatch * n below 2^31, nmatch and ngroups below 2^24");

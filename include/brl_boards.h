@@ -80,7 +80,8 @@ typedef struct brl_board_record {
 int brl_board_records(int device, const uint64_t *state, int64_t n, brl_board_record *records, void *stream);
 
 /* out_imp[i] (int32) = the IMP (src/duplicate.py:15-70) the pair sitting North-South at table A wins on board i, whose other
- * pair sits North-South at table B: the conversion of records_a[i].score_ns - records_b[i].score_ns. */
+ * pair sits North-South at table B: the conversion of records_a[i].score_ns - records_b[i].score_ns.  records_a / records_b
+ * 8-byte aligned (the struct's own alignment), out_imp 4-byte. */
 int brl_board_imp(int device, const brl_board_record *records_a, const brl_board_record *records_b, int64_t n, int32_t *out_imp,
                   void *stream);
 
@@ -93,7 +94,8 @@ int brl_board_imp(int device, const brl_board_record *records_a, const brl_board
  *   taken       uint8  [n]     in/out: 1 once final_a[i] is written (start with zeros)
  *   final_a     uint64 [n,16]  out: for a table whose a_done turned 1 in this step, prev[i] stepped by action[i] with
  *                              bridge_device.hpp's table_step — the state the step kernel had in hand before the hand-over
- * One launch, a thread per table. */
+ * One launch, a thread per table.  state, prev and final_a 16-byte aligned (a table's row is moved as 16-byte pieces), action
+ * 4-byte; BRL_E_ARG otherwise, before anything is launched. */
 int brl_board_keep_a(int device, const uint64_t *state, uint64_t *prev, const int32_t *action, const uint8_t *a_done,
                      uint8_t *taken, uint64_t *final_a, int64_t n, void *stream);
 

@@ -48,7 +48,8 @@ extern "C" {
  * both halves' counts written), an exclusive scan over the positions of the order by one workgroup, a compacting scatter (a
  * wave per match again, both halves' first rows in hand) — no atomics, a fixed order, the same bytes on every run.
  * nmatch * n < 2^31.  Entries of order / group_of outside their range are clamped, and a row whose place would lie outside
- * rows[0 .. nmatch * n) is not written (an order that is not a permutation): the result may be wrong, never an address. */
+ * rows[0 .. nmatch * n) is not written (an order that is not a permutation): the result may be wrong, never an address.
+ * Alignment as brl_league_route's: rows 8-byte, the int32 arrays 4-byte. */
 int brl_xplay_route(int device, const uint8_t *terminated, const int32_t *current_player, int team, int64_t n,
                     const int32_t *order, const int32_t *group_of, int64_t nmatch, int64_t ngroups, int32_t *work,
                     int64_t *rows, int32_t *group_first, void *stream);

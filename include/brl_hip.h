@@ -89,7 +89,8 @@ int brl_init_random(brl_handle *h, uint64_t *state, int64_t n, uint32_t board_ct
 /* Explicit deals — the fields _duplicate_init copies (src/duplicate.py:120-128).
  * hand int32 [n,52] (13 pgx card ids per seat N,E,S,W), dealer int32 [n], vul_ns/vul_ew
  * uint8 [n], shuffled_players int32 [n,4] (seat -> player id), tricks uint8 [n,20]
- * ([declarer seat][C,D,H,S,NT]). */
+ * ([declarer seat][C,D,H,S,NT]).  Every array as its element type: state 8-byte aligned, int32 4-byte
+ * (BRL_E_ARG otherwise, before anything is launched). */
 int brl_init_from_deals(brl_handle *h, uint64_t *state, int64_t n, const int32_t *hand,
                         const int32_t *dealer, const uint8_t *vul_ns, const uint8_t *vul_ew,
                         const int32_t *shuffled_players, const uint8_t *tricks, void *stream);
@@ -113,7 +114,9 @@ int brl_step(brl_handle *h, const uint64_t *state_in, uint64_t *state_out, int64
 int brl_observe(brl_handle *h, const uint64_t *state, int64_t n, const int32_t *player_id,
                 uint8_t *obs, uint8_t *mask, void *stream);
 
-/* State attribute access (pgx State fields).  Every pointer may be NULL. */
+/* State attribute access (pgx State fields).  Every pointer may be NULL.  Alignment: rewards 16-byte (a
+ * table's four floats are ONE store, as brl_step's), every other member as its element type (int32 / uint32 4-byte); state
+ * 8-byte; BRL_E_ARG otherwise, before anything is launched. */
 typedef struct brl_fields {
   int32_t *current_player;        /* [n]    */
   uint8_t *terminated;            /* [n]    */
@@ -288,10 +291,13 @@ int brl_gae(brl_handle *h, const uint8_t *done, const float *value, const float 
             const float *last_val, float gamma, float gamma_lambda, int T, int64_t n,
             float *advantages, float *targets, void *stream);
 
-/* _imp_reward — src/duplicate.py:15-70.  a, b, out float [n,4]. */
+/* _imp_reward — src/duplicate.py:15-70.  a, b, out float [n,4].  out 16-byte aligned (a board's IMP vector is ONE store);
+ * a, b 4-byte (only the first float of a row is read); BRL_E_ARG otherwise, before anything is launched. */
 int brl_imp_reward(brl_handle *h, const float *a, const float *b, float *out, int64_t n, void *stream);
 
-/* Table_info — src/duplicate.py:138-144 (struct of arrays). */
+/* Table_info — src/duplicate.py:138-144 (struct of arrays).  rewards 16-byte aligned (a board's four floats move as ONE
+ * piece in brl_duplicate_step / brl_eval_step / brl_eval_step_team), last_bid / last_bidder 4-byte: every entry point that
+ * takes the struct answers BRL_E_ARG otherwise, before anything is launched. */
 typedef struct brl_table_info {
   uint8_t *terminated;  /* [n]   */
   float *rewards;       /* [n,4] */
@@ -302,7 +308,8 @@ typedef struct brl_table_info {
 } brl_table_info;
 
 /* duplicate_step(env.step) — src/duplicate.py:147-192; table_a/table_b updated in place.
- * Optional outputs as brl_step (rewards = the IMP vector on the step table B ends, else 0). */
+ * Optional outputs as brl_step (rewards = the IMP vector on the step table B ends, else 0), aligned and checked as brl_step's:
+ * state 8-byte, obs 8, rewards 16, action / current_player 4. */
 int brl_duplicate_step(brl_handle *h, const uint64_t *state_in, uint64_t *state_out, int64_t n,
                        const int32_t *action, const brl_table_info *table_a,
                        const brl_table_info *table_b, uint8_t *obs, uint8_t *mask, float *rewards,
@@ -322,7 +329,10 @@ typedef struct brl_eval_stats {
  * (players {0,1}: logits_team1, else logits_team2; float [n,38] with row strides) plays masked_pi.mode(); boards that
  * are not finished update `stats`; then duplicate_step (table_a/table_b given, src/duplicate.py:147-192) or env.step
  * (both NULL); cum_return float [n] += rewards[0], rewards_sum float [n,4] += rewards (either may be NULL);
- * action_out int32 [n] (may be NULL).  Remaining outputs as brl_step. */
+ * action_out int32 [n] (may be NULL).  Remaining outputs as brl_step.
+ * Alignment: state, obs, rewards and current_player as brl_step's (8 / 8 / 16 / 4); rewards_sum 16-byte (a board's four sums
+ * are read and written as ONE piece); logits, cum_return, action_out and every member of `stats` 4-byte; the tables as
+ * brl_table_info says.  BRL_E_ARG otherwise, before anything is launched (brl_eval_step_team too). */
 int brl_eval_step(brl_handle *h, const uint64_t *state_in, uint64_t *state_out, int64_t n,
                   const float *logits_team1, int64_t stride1, const float *logits_team2, int64_t stride2,
                   const brl_table_info *table_a, const brl_table_info *table_b, const brl_eval_stats *stats,
@@ -352,7 +362,8 @@ int brl_eval_step_team(brl_handle *h, const uint64_t *state_in, uint64_t *state_
  *   out[t*80 + 9]                                    sum of rewards[0] (table scores are integers)
  *   out[t*80 + 10 + 35*team + bid]                   final contracts by declaring team and bid
  *   out[160 + 35*team + bid]                         sum over boards of stats.bid_count (bid_count may be NULL)
- *   out[230]                                         sum of _step_count of `state` (may be NULL) */
+ *   out[230]                                         sum of _step_count of `state` (may be NULL)
+ * bid_count 8-byte aligned (a board's 70 counters are read as 35 pairs), state and out 8-byte; BRL_E_ARG otherwise. */
 #define BRL_EVAL_COUNTS 231
 int brl_eval_reduce(brl_handle *h, int64_t n, const brl_table_info *table_a, const brl_table_info *table_b,
                     const int32_t *bid_count, const uint64_t *state, int64_t *out, void *stream);

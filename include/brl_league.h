@@ -44,7 +44,8 @@ typedef struct brl_league_net {
  *                                    group_first[ngroups] = R
  *   work        int32 [2 * nmatch]   scratch (per slot: its count, then its first row)
  * Three launches — counts per slot (one wave per match: ballot + popcount), an exclusive scan by one workgroup, a compacting
- * scatter — no atomics, a fixed order.  nmatch * n < 2^31. */
+ * scatter — no atomics, a fixed order.  nmatch * n < 2^31.  Every array as its element type: rows 8-byte aligned, the int32
+ * arrays 4-byte (BRL_E_ARG otherwise, before anything is launched). */
 int brl_league_route(int device, const uint8_t *terminated, const int32_t *current_player, int team, int64_t n,
                      const int32_t *order, const int32_t *group_of, int64_t nmatch, int64_t ngroups, int32_t *work,
                      int64_t *rows, int32_t *group_first, void *stream);
@@ -58,7 +59,9 @@ int brl_league_route(int device, const uint8_t *terminated, const int32_t *curre
  *     rmax >= R  and  ngroups,
  * (floor(rmax / 64) + ngroups row tiles per layer), and workgroups beyond the real work return at once.
  * nets: device array [ngroups]; nlayers 1..8, hidden a multiple of 4 and <= 1024, act 0 = ReLU / 1 = tanh — shared by all
- * networks.  obs uint8 [boards, 480]; scratch: rmax * (480 + 2 * hidden) floats, 16-byte aligned; ldo >= 39. */
+ * networks.  obs uint8 [boards, 480], 4-byte aligned (a row is read as 4-byte words, as brl_mlp_forward_rows'); scratch:
+ * rmax * (480 + 2 * hidden) floats, 16-byte aligned; rows and nets 8-byte, group_first and out 4-byte; ldo >= 39.  BRL_E_ARG
+ * otherwise, before anything is launched (the arrays the records of `nets` name are on the device: not checked). */
 int brl_league_forward(int device, const brl_league_net *nets, int64_t ngroups, int nlayers, int64_t hidden, int act,
                        const uint8_t *obs, const int64_t *rows, const int32_t *group_first, int64_t rmax, float *scratch,
                        int64_t scratch_len, float *out, int64_t ldo, void *stream);

@@ -15,7 +15,7 @@ The logical elements of an OUTPUT start as a NaN / negative-integer variant of t
 nearest array, row, column and byte offset of the first difference.
 
 Also here: ``Plain`` / ``Guarded`` / ``both`` — the two ways a GPU case gets its arrays, and the comparison of the two runs
-(tests/test_gpu_memory_contract.py and tests/test_gpu_memory_contract_update.py) — and the ledger of which C-ABI entry points run under these guards (``COVERED``) and which do not yet (``OPEN``);
+(tests/test_gpu_memory_contract.py, tests/test_gpu_memory_contract_update.py and tests/test_gpu_memory_contract_match.py) — and the ledger of which C-ABI entry points run under these guards (``COVERED``) and which do not yet (``OPEN``);
 tests/test_guarded_host.py holds every ``int brl_*(`` declaration of include/*.h against the two.
 """
 from __future__ import annotations
@@ -131,6 +131,17 @@ class Arena:
             if self.base + r.off == p:
                 return r
         raise KeyError("not a placed array of this arena")
+
+    def signalling_margins(self, view, nbytes=64):
+        """The `nbytes` guard bytes in front of and behind a placed fp32 array become signalling NaNs (0x7FA0 over two pattern
+        bytes).  For an accumulator updated in place: a read-modify-write that reaches one element too far and adds 0.0 stores the
+        bytes it read — no guard byte changes — unless they are a signalling NaN, which the add returns quiet: other bits."""
+        r = self.rec(view)
+        assert r.itemsize == 4 and nbytes % 4 == 0 and 0 < nbytes <= GUARD // 2
+        for lo in (r.off - nbytes, r.off + r.extent):
+            w = self.expected[lo:lo + nbytes].reshape(-1, 4)
+            w[:, 2], w[:, 3] = 0xA0, 0x7F
+            self.buf[lo:lo + nbytes].copy_(torch.from_numpy(self.expected[lo:lo + nbytes]))
 
     # ---- checking ------------------------------------------------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
@@ -259,8 +270,8 @@ def round_up(x: int, q: int) -> int:
 
 
 # ---- the ledger: every `int brl_*(` of include/*.h is in exactly one of the two ------------------------------------------------
-# COVERED: entry point -> what tests/test_gpu_memory_contract.py (the PPO step's own entry points: tests/test_gpu_memory_contract_update.py)
-# runs it on (alignments, strides, shapes)
+# COVERED: entry point -> what tests/test_gpu_memory_contract.py (the PPO step's own entry points: tests/test_gpu_memory_contract_update.py;
+# the entry points that play and record a match: tests/test_gpu_memory_contract_match.py) runs it on (alignments, strides, shapes)
 COVERED = {
     "brl_mlp_gemm": "a / b / c / bias / gate at 16 bytes, colsum / sqsum at 4 and exactly sized; lda / ldb / ldc / ldg = dense + 4; NT, NN, TN x "
                     "every epilogue at (4,4,4), (68,36,52), (60,132,8); 64 x 32 tiles, and 64 x 64 in a child process (BRL_GEMM_TILE_N=64)",
@@ -327,6 +338,32 @@ COVERED = {
     "brl_fair_forward": "rows in {1, 17}; x and the weights at 16, head_b / logits [rows, 38] / value [rows] at 4 and exactly sized",
     "brl_fair_chain": "batch in {16, 48}; every brl_fair_work array its own placement at 16, exactly the header's size; gram_partials given and NULL; "
                       "both activations",
+    "brl_init_from_deals": "n in {1, 3, 33, 65}; int32 arrays at 4, uint8 at 1, state at 8; the deals of stepped env.init tables: the rebuilt state's "
+                           "fields equal oracle.init_explicit's",
+    "brl_get_fields": "n in {1, 3, 33, 65}; live, finished and illegally ended tables; state at 8, every brl_fields member its own placement: int32 at 4, "
+                      "uint8 at 1, rewards at 16; every member given, and every one NULL but `turn`",
+    "brl_imp_reward": "n in {1, 3, 33, 65}; a / b at 4, out at 16; scores with +-7600 and 0",
+    "brl_duplicate_step": "n in {1, 3, 33}, eight scripted launches through both hand-overs; states at 8, both brl_table_info blocks in place with every member "
+                          "its own placement (rewards at 16, int32 at 4, uint8 at 1), every launch's outputs placements of their own (obs at 8, rewards "
+                          "at 16); every optional output given, and every one NULL",
+    "brl_eval_step": "n in {1, 3, 33}, eight launches in place; logits at strides 38 and 40 (NaN in columns 38, 39); tables and brl_eval_stats members each "
+                     "placed (rewards / rewards_sum at 16, the rest at 4 / 1); stats NULL, bid_count NULL, all given; bid_set 0 and 1; accumulators, "
+                     "step outputs given and NULL; duplicate and single-table form",
+    "brl_eval_step_team": "as brl_eval_step over eleven launches, acting_team alternating; obs_f32 at 16 and NULL; waiting boards keep the bits of state, "
+                          "statistics and accumulators, action_out -1",
+    "brl_eval_reduce": "n in {1, 3, 257}; tables read only (rewards at 16), bid_count at 8, state at 8, out int64 [231] at 8 and exactly sized; table_b, "
+                       "bid_count and state each given and NULL",
+    "brl_league_route": "(nmatch, n) in {(1,1), (3,5), (4,65)}, ngroups in {1, 3} (one group empty), team 0 and 1; terminated at 1, int32 at 4, rows at 8; "
+                        "work exactly 2 nmatch, group_first exactly ngroups + 1; rows from R on untouched",
+    "brl_xplay_route": "as brl_league_route; work exactly 4 nmatch (2 per slot)",
+    "brl_league_forward": "hidden in {64, 260}, nlayers in {1, 3}, two networks (one with a single row), both activations; every weight / hidden bias at 16, "
+                          "head biases at 4, the records at 8, obs at 4, rows at 8; scratch at 16, exactly rmax (480 + 2 hidden) floats, rmax = R and "
+                          "R + 64; ldo in {40, 44}; unrouted rows of out untouched",
+    "brl_board_records": "n in {1, 3, 65, 130}; state at 8, records at 16 and exactly n * 368 bytes; the 319-call auction, pass-outs, live, contract and "
+                         "illegally ended tables",
+    "brl_board_imp": "the same n; records at 16, out_imp at 4",
+    "brl_board_keep_a": "n in {1, 3, 65}, behind five alternating launches of the scripted match; state / prev / final_a at 16, taken / a_done at 1, action at 4 "
+                        "with -1 entries; final_a rows of boards whose table A has not ended untouched",
 }
 
 _NOT_YET = "not yet placed in an arena: "
@@ -342,12 +379,9 @@ OPEN = {
 for _n, _why in {
     "brl_policy_step": "brl_policy_step_ex with dense logits and no ext block (the same kernel, guarded there)",
     "brl_policy_step_at": "brl_policy_step_ex without the ext block (the same kernel, guarded there)",
-    "brl_init_from_deals": "", "brl_get_fields": "", "brl_imp_reward": "", "brl_duplicate_step": "",
-    "brl_eval_step": "", "brl_eval_step_team": "", "brl_eval_reduce": "",
-    "brl_league_route": "", "brl_league_forward": "", "brl_board_records": "", "brl_board_imp": "", "brl_board_keep_a": "",
     "brl_book_samples": "", "brl_book_reduce": "", "brl_par": "", "brl_par_imp": "", "brl_review_expand": "", "brl_review_reduce": "",
     "brl_belief_deal": "", "brl_belief_logp": "", "brl_belief_reduce": "", "brl_belief_resample": "", "brl_belief_propose": "",
-    "brl_belief_accept": "", "brl_compare_tables": "", "brl_compare_rows": "", "brl_compare_reduce": "", "brl_xplay_route": "",
+    "brl_belief_accept": "", "brl_compare_tables": "", "brl_compare_rows": "", "brl_compare_reduce": "",
     "brl_lines_init": "", "brl_lines_expand": "", "brl_lines_finish": "", "brl_lines_imp": "",
 }.items():
     OPEN[_n] = _NOT_YET + (_why or "compared with its reference on dense torch tensors only")

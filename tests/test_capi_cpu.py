@@ -184,6 +184,94 @@ def test_handle_entry_points_refuse_misaligned_pointers_before_anything_else(bui
     assert pol(ctypes.byref(_capi.MacroExt(obs_cast=P))) == -1 and b"handle" in L.brl_last_error()
 
 
+def test_match_entry_points_refuse_misaligned_pointers_before_anything_else(built_lib):
+    """The entry points that play and record a match (tests/test_gpu_memory_contract_match.py runs them under the guards): what
+    their kernels move in pieces wider than the element type — brl_table_info.rewards, rewards, rewards_sum, brl_fields.rewards,
+    brl_imp_reward's out, brl_board_keep_a's tables at 16 bytes, brl_eval_reduce's bid_count at 8, brl_league_forward's obs at 4 —
+    and every array's own element type: asked for with made-up addresses and no handle, so nothing is read and nothing launched."""
+    from brl_amd import _capi
+    L = _capi.lib()
+    P = 0x7F0000000000
+
+    def refused(rc, what):
+        assert rc == -1 and what in L.brl_last_error(), (rc, L.brl_last_error())
+
+    def table(**k):
+        t = _capi.TableInfoPtrs()
+        for name in _capi.TableInfoPtrs._names:
+            setattr(t, name, k.get(name, P + 1 if name in ("terminated", "call_x", "call_xx") else P))
+        return ctypes.byref(t)
+    bad_tables = (dict(rewards=P + 4), dict(rewards=P + 8), dict(last_bid=P + 2), dict(last_bidder=P + 2))
+    dup = lambda ta=None, tb=None, **k: L.brl_duplicate_step(None, k.get("si", P), k.get("so", P), 4, k.get("act", P), ta or table(),   # noqa: E731
+                                                             tb or table(), k.get("obs", P), P + 1, k.get("rew", P), P + 1, k.get("cur", P), None)
+    for kw in (dict(si=P + 4), dict(so=P + 4), dict(act=P + 2), dict(obs=P + 4), dict(rew=P + 4), dict(rew=P + 8), dict(cur=P + 2)):
+        refused(dup(**kw), b"rewards not 16-byte")
+    for bad in bad_tables:
+        refused(dup(ta=table(**bad)), b"table_a / table_b: rewards not 16-byte")
+        refused(dup(tb=table(**bad)), b"table_a / table_b: rewards not 16-byte")
+    assert dup() == -1 and b"handle" in L.brl_last_error()
+
+    def stats(**k):
+        s = _capi.EvalStatsPtrs()
+        for name in _capi.EvalStatsPtrs._names:
+            setattr(s, name, k.get(name, P))
+        return ctypes.byref(s)
+
+    def ev(team, ta=None, tb=None, st=None, **k):
+        tail = (ta or table(), tb or table(), st, 0, k.get("cum", P), k.get("rsum", P), k.get("aout", P), k.get("obs", P), P + 1,
+                k.get("rew", P), P + 1, k.get("cur", P))
+        if team:
+            return L.brl_eval_step_team(None, k.get("si", P), k.get("so", P), 4, k.get("lg", P), 38, 0, *tail, k.get("f32", P), None)
+        return L.brl_eval_step(None, k.get("si", P), k.get("so", P), 4, k.get("lg", P), 38, k.get("lg2", P), 38, *tail, None)
+    for team in (False, True):
+        for kw in (dict(si=P + 4), dict(so=P + 4), dict(obs=P + 4), dict(rew=P + 4), dict(cur=P + 2)):
+            refused(ev(team, **kw), b"rewards not 16-byte")
+        for bad in bad_tables:
+            refused(ev(team, tb=table(**bad)), b"table_a / table_b: rewards not 16-byte")
+        for kw in (dict(rsum=P + 4), dict(rsum=P + 8), dict(cum=P + 2), dict(aout=P + 2), dict(lg=P + 2)):
+            refused(ev(team, **kw), b"rewards_sum not 16-byte aligned")
+        for name in _capi.EvalStatsPtrs._names:
+            refused(ev(team, st=stats(**{name: P + 2})), b"rewards_sum not 16-byte aligned")
+        assert ev(team, st=stats()) == -1 and b"handle" in L.brl_last_error()
+    refused(ev(False, lg2=P + 2), b"rewards_sum not 16-byte aligned")
+    refused(ev(True, f32=P + 4), b"obs_f32 not 16-byte aligned")
+    red = lambda ta=None, tb=None, **k: L.brl_eval_reduce(None, 4, ta or table(), tb, k.get("bc", P), k.get("st", P), k.get("out", P), None)   # noqa: E731
+    for kw in (dict(bc=P + 4), dict(st=P + 4), dict(out=P + 4)):
+        refused(red(**kw), b"bid_count / state / out not 8-byte aligned")
+    refused(red(ta=table(rewards=P + 4)), b"table_a / table_b: rewards not 16-byte")
+    refused(red(tb=table(rewards=P + 4)), b"table_a / table_b: rewards not 16-byte")
+    assert red() == -1 and b"handle" in L.brl_last_error()
+    for out in (P + 4, P + 8):
+        refused(L.brl_imp_reward(None, P, P, out, 4, None), b"out not 16-byte aligned")
+    refused(L.brl_imp_reward(None, P + 2, P, P, 4, None), b"out not 16-byte aligned")
+    assert L.brl_imp_reward(None, P + 4, P + 4, P, 4, None) == -1 and b"handle" in L.brl_last_error()
+    for name, off in (("rewards", 4), ("rewards", 8), ("hand", 2), ("board_ctr", 2)):
+        f = _capi.Fields()
+        setattr(f, name, P + off)
+        refused(L.brl_get_fields(None, P, 4, ctypes.byref(f), None), b"rewards not 16-byte")
+    refused(L.brl_get_fields(None, P + 4, 4, ctypes.byref(_capi.Fields()), None), b"state not 8-byte aligned")
+    refused(L.brl_init_from_deals(None, P + 4, 4, P, P, P + 1, P + 1, P, P + 1, None), b"state not 8-byte aligned")
+    refused(L.brl_init_from_deals(None, P, 4, P + 2, P, P + 1, P + 1, P, P + 1, None), b"state not 8-byte aligned")
+    assert L.brl_init_from_deals(None, P, 4, P, P, P + 1, P + 1, P, P + 1, None) == -1 and b"handle" in L.brl_last_error()
+    DEV = 1 << 20     # (no such device: an aligned call fails at hipSetDevice, behind every argument check)
+    keep = lambda **k: L.brl_board_keep_a(DEV, k.get("st", P), k.get("prev", P), k.get("act", P), P + 1, P + 1, k.get("fin", P), 4, None)   # noqa: E731
+    for kw in (dict(st=P + 8), dict(prev=P + 8), dict(fin=P + 8), dict(fin=P + 4), dict(act=P + 2)):
+        refused(keep(**kw), b"state / prev / final_a 16-byte aligned")
+    assert keep() == -2
+    refused(L.brl_board_imp(DEV, P + 4, P, 4, P, None), b"records 8-byte aligned")
+    refused(L.brl_board_imp(DEV, P, P, 4, P + 2, None), b"records 8-byte aligned")
+    fwd = lambda **k: L.brl_league_forward(DEV, k.get("nets", P), 1, 1, 64, 0, k.get("obs", P), k.get("rows", P), k.get("gf", P), 1, P, 608,   # noqa: E731
+                                           k.get("out", P), 40, None)
+    for kw in (dict(obs=P + 2), dict(obs=P + 1), dict(rows=P + 4), dict(nets=P + 4), dict(gf=P + 2), dict(out=P + 2)):
+        refused(fwd(**kw), b"obs / group_first / out not 4-byte aligned")
+    assert fwd(obs=P + 4) == -2
+    for fn in (L.brl_league_route, L.brl_xplay_route):
+        route = lambda **k: fn(DEV, P + 1, k.get("cur", P), 0, 4, k.get("order", P), P, 2, 1, k.get("work", P), k.get("rows", P), k.get("gf", P), None)   # noqa: E731
+        for kw in (dict(cur=P + 2), dict(order=P + 2), dict(work=P + 2), dict(rows=P + 4), dict(gf=P + 2)):
+            refused(route(**kw), b"rows not 8-byte")
+        assert route() == -2
+
+
 def test_update_entry_points_refuse_misaligned_pointers_before_anything_else(built_lib):
     """The PPO step's entry points (include/brl_hip.h states the alignment of every pointer argument): each pointer in turn is
     moved to half its alignment — 16-byte ones to P + 8, 8-byte ones to P + 4, 4-byte ones to P + 2 — and the call must come back

@@ -108,6 +108,24 @@ def test_a_store_into_an_input_is_caught_unless_it_is_inout():
     a.check()
 
 
+def test_signalling_margins_show_an_add_of_zero():
+    """an accumulator updated in place for one element too many: `x + 0.0` stores x's own bits on the pattern (nothing to see), and a
+    quiet NaN on a signalling margin"""
+    a = Arena()
+    acc = a.place((3, 4), torch.float32, 16, fill=torch.zeros(3, 4), name="rewards_sum", inout=True)
+    r = a.rec(acc)
+    behind = a.buf[r.off + r.extent:r.off + r.extent + 16].view(torch.float32)      # "table 3" of a [3, 4] array
+    behind += 0.0
+    a.check()                                     # the pattern: the same bytes came back
+    a.signalling_margins(acc)
+    a.check()                                     # placing the margins changes nothing by itself
+    assert bool(torch.isnan(behind).all())
+    word = int(behind.view(torch.int32)[0]) | 0x00400000      # what an IEEE add returns for a signalling NaN: the same NaN, quiet
+    behind.view(torch.int32)[0] = word
+    with pytest.raises(GuardError, match=r"guard byte changed .*3 byte\(s\) BEHIND array 'rewards_sum'.*placed 0xa0, found 0xe0"):
+        a.check()
+
+
 def test_allowed_padding_takes_zeros_and_nothing_else():
     n_heads, ld = 39, 44
     a = Arena()
