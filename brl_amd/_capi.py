@@ -171,6 +171,7 @@ def lib() -> C.CDLL:
     sigs.update(crossplay_argtypes())
     sigs.update(distill_argtypes())
     sigs.update(lines_argtypes())
+    sigs.update(positions_argtypes())
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -304,6 +305,15 @@ def lines_argtypes() -> dict:
         "brl_lines_expand": [i32, _vp, _vp, _vp, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "brl_lines_finish": [i32, _vp, _vp, i64, _vp, _vp],
         "brl_lines_imp": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, i32, _vp, _vp],
+    }
+
+
+def positions_argtypes() -> dict:
+    """argtypes of include/brl_positions.h (the position queries; not part of brl_hip.h nor of EXPORTS)"""
+    i64, i32 = C.c_int64, C.c_int
+    return {
+        "brl_position_rows": [i32, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp],
+        "brl_position_answers": [i32, _vp, i64, _vp, i64, _vp, _vp, i64, i32, _vp, _vp, _vp],
     }
 
 

@@ -2,7 +2,8 @@
 // k_compare_tables builds the empty tables of the listed records' deals with the beliefs' builder (belief_table.hpp).
 // k_compare_rows writes one call index's decision records: eight lanes per row, categorical<8> (policy_common.hpp) in mode form
 // per network for the call and the played call's log-probability as k_belief_logp forms it, then the float64 divergences on
-// the same lane layout (five actions per lane, the eight slot sums added in ascending slot order).
+// the same lane layout (five actions per lane, the eight slot sums added in ascending slot order; each network's p_a and L_a by
+// policy_dist.hpp, which the position queries share).
 // k_compare_reduce sums a key's run of sorted decisions into its entry: a workgroup per entry, a thread per block of 64
 // decisions, the block sums added in ascending order by one thread per sum; integers through LDS atomics.
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "bridge_device.hpp"
 #include "hand_features.hpp"
 #include "policy_common.hpp"
+#include "policy_dist.hpp"
 
 namespace {
 
@@ -58,54 +60,6 @@ __global__ __launch_bounds__(BELIEF_LANES) void k_compare_tables(const uint4 *re
 }
 
 // ---- one call index's decisions ---------------------------------------------------------------------------------------------------
-constexpr int ROW_LANES = 8;    // lanes per row: categorical<8>
-constexpr int NI = 5;           // actions per lane: slot k holds 5 k .. 5 k + 4
-
-// the eight slot values of a row added in ascending slot order; the same bits on every lane of the row
-__device__ __forceinline__ double slot_sum(double own, int tl) {
-#pragma clang fp contract(off)
-  double s = __shfl(own, tl, 64);
-#pragma unroll
-  for (int k = 1; k < 64 / ROW_LANES; k++) s += __shfl(own, k * ROW_LANES + tl, 64);
-  return s;
-}
-
-__device__ __forceinline__ bool row_any(bool x) {
-  int v = x ? 1 : 0;
-#pragma unroll
-  for (int off = ROW_LANES; off < 64; off <<= 1) v |= __shfl_xor(v, off, 64);
-  return v != 0;
-}
-
-// p_a and L_a = log p_a of this lane's five actions (brl_compare.h); `bad`: the network's NONFINITE condition, row-wide
-__device__ __forceinline__ void net_dist(const float *row, uint64_t legal, int amax, int slot, int tl, double p[NI], double L[NI],
-                                         bool &bad) {
-#pragma clang fp contract(off)
-  const double m = (double)row[amax];
-  float lf[NI];
-#pragma unroll
-  for (int i = 0; i < NI; i++) lf[i] = row[min(slot * NI + i, ACTIONS - 1)];
-  double x[NI], e[NI], own = 0.0;
-  bool nonfinite = false, live = false;
-#pragma unroll
-  for (int i = 0; i < NI; i++) {
-    const int a = slot * NI + i;
-    const bool ok = a < ACTIONS && ((legal >> (a & 63)) & 1ull);
-    nonfinite |= ok && (lf[i] != lf[i] || lf[i] == INFINITY);
-    live |= ok && lf[i] > -INFINITY;
-    x[i] = (double)lf[i] - m;
-    e[i] = ok ? exp(x[i]) : 0.0;
-    own += e[i];
-  }
-  const double S = slot_sum(own, tl), logS = log(S);
-#pragma unroll
-  for (int i = 0; i < NI; i++) {
-    p[i] = e[i] / S;
-    L[i] = x[i] - logS;
-  }
-  bad = row_any(nonfinite) || !row_any(live);
-}
-
 // KL(first || second) over this lane's actions: p * (L - Lo), +0.0 where p == 0
 __device__ __forceinline__ double kl_own(const double p[NI], const double L[NI], const double Lo[NI]) {
 #pragma clang fp contract(off)
