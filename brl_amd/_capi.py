@@ -71,12 +71,151 @@ class FairWork(C.Structure):
     _fields_ = [(n, _vp) for n in _names]
 
 
+class LeagueNet(C.Structure):
+    """brl_league_net (include/brl_league.h): one "DeepMind" fp32 network by reference, 20 device pointers"""
+    _fields_ = [("w", _vp * 8), ("b", _vp * 8), ("actor_w", _vp), ("actor_b", _vp), ("critic_w", _vp), ("critic_b", _vp)]
+
+
 EVAL_COUNTS = 231  # BRL_EVAL_COUNTS
 
 
 class BrlError(RuntimeError):
     pass
 
+
+def _signatures() -> dict:
+    """the argtypes of every `int brl_*(` entry point, keyed by the header of include/ that declares it (tests/test_capi_cpu.py holds
+    every prototype of every header against this table)"""
+    i64, i32, u32, u64, f32 = C.c_int64, C.c_int, C.c_uint32, C.c_uint64, C.c_float
+    return {
+        "brl_hip.h": {
+            "brl_version": [],
+            "brl_create": [i32, _vp, _vp, i64, C.POINTER(_vp)],
+            "brl_set_lut": [_vp, _vp, _vp, i64],
+            "brl_destroy": [_vp],
+            "brl_set_rng": [_vp, u64, u64],
+            "brl_init_random": [_vp, _vp, i64, u32, _vp],
+            "brl_init_from_deals": [_vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_step": [_vp, _vp, _vp, i64, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_observe": [_vp, _vp, i64, _vp, _vp, _vp, _vp],
+            "brl_get_fields": [_vp, _vp, i64, C.POINTER(Fields), _vp],
+            "brl_rollout_random": [_vp, _vp, i64, i32, i32, u32, f32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp],
+            "brl_rollout_random_gae": [_vp, _vp, i64, i32, u32, f32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp, f32, f32, _vp, _vp,
+                                       _vp],
+            "brl_policy_step": [_vp, _vp, _vp, i64, _vp, i32, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_policy_step_at": [_vp, _vp, _vp, i64, _vp, i64, i32, _vp, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_policy_step_ex": [_vp, _vp, _vp, i64, _vp, i64, i32, _vp, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(MacroExt), _vp],
+            "brl_obs_cast": [_vp, _vp, i64, _vp, i32, _vp],
+            "brl_obs_cast_rows": [_vp, _vp, _vp, i64, _vp, i32, _vp],
+            "brl_live_index": [_vp, _vp, i64, _vp, _vp, i64, _vp],
+            "brl_linear_act_heads": [_vp, _vp, i64, _vp, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, _vp, i64, i32, _vp, i64, i64, _vp],
+            "brl_linear_act": [_vp, _vp, i64, _vp, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, _vp],
+            "brl_gae": [_vp, _vp, _vp, _vp, _vp, f32, f32, i32, i64, _vp, _vp, _vp],
+            "brl_imp_reward": [_vp, _vp, _vp, _vp, i64, _vp],
+            "brl_duplicate_step": [_vp, _vp, _vp, i64, _vp, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
+                                   _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_eval_step": [_vp, _vp, _vp, i64, _vp, i64, _vp, i64, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
+                              C.POINTER(EvalStatsPtrs), i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_eval_step_team": [_vp, _vp, _vp, i64, _vp, i64, i32, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
+                                   C.POINTER(EvalStatsPtrs), i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_eval_reduce": [_vp, i64, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs), _vp, _vp, _vp, _vp],
+            "brl_ppo_loss": [i32, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, _vp, _vp, _vp, _vp, _vp],
+            "brl_ppo_stats": [i32, _vp, i64, _vp, f32, f32, _vp, _vp],
+            "brl_ppo_heads_loss_split": [i32, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, i32, _vp, _vp, _vp, _vp, _vp, i32, _vp],
+            "brl_ppo_heads_bwd": [i32, _vp, _vp, i64, _vp, i64, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
+            "brl_ppo_stats_rows": [i32, _vp, _vp, i64, i64, f32, f32, f32, _vp, _vp],
+            "brl_mb_gather_bind": [i32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp, _vp],
+            "brl_adam_clip_fin_gather": [i32, _vp, _vp, _vp, _vp, i64, _vp, f32, _vp, f32, f32, f32, f32, _vp, i64, _vp, _vp, _vp, i64,
+                                         i32, _vp, _vp, _vp, _vp, _vp],
+            "brl_mb_gather_dev": [i32, _vp, i64, _vp],
+            "brl_ppo_stats_gram": [i32, _vp, i64, i64, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp],
+            "brl_ppo_illegal_grad": [i32, _vp, _vp, _vp, f32, i64, _vp, _vp],
+            "brl_act_bwd_colsum": [i32, _vp, _vp, i64, i64, i64, i32, _vp, _vp],
+            "brl_act_bwd_colsum_heads_dw": [i32, _vp, _vp, i64, i64, i64, i32, _vp, _vp, _vp, i64, i64, i64, i32, _vp, _vp, _vp, _vp, i64,
+                                            _vp, _vp, _vp, _vp],
+            "brl_bias_finalize_ex": [i32, i32, _vp, _vp, _vp, _vp, _vp],
+            "brl_bias_finalize_rows": [i32, i32, _vp, _vp, _vp, _vp, i32, _vp, _vp],
+            "brl_fair_forward": [i32, C.POINTER(FairNet), _vp, i64, i32, _vp, _vp, _vp],
+            "brl_mlp_gemm_group": [i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_fair_chain": [i32, C.POINTER(FairNet), _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, i32, i32,
+                               C.POINTER(FairWork), _vp],
+            "brl_mlp_gemm": [i32, i32, i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, _vp, i64, _vp, _vp, _vp],
+            "brl_mlp_gemm_x3_workspace": [i64, i64, i64, _vp],
+            "brl_mlp_gemm_x3_group": [i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_split_planes": [i32, _vp, i64, _vp, i64, _vp],
+            "brl_linear_x3p": [i32, _vp, i32, i64, i64, _vp, i64, i64, _vp, i32, _vp, i64, _vp, i64, i64, i64, i64, i64, _vp],
+            "brl_mlp_gemm_x3": [i32, i32, i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, _vp, i64, _vp, _vp, i64, _vp],
+            "brl_mlp_forward_rows": [i32, C.POINTER(MlpRef), _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
+            "brl_adam_shard_norm": [i32, _vp, C.POINTER(ShardGeom), i32, i32, f32, _vp, _vp, _vp, _vp],
+            "brl_adam_shard_apply": [i32, _vp, _vp, _vp, _vp, C.POINTER(ShardGeom), i32, i32, _vp, _vp, f32, _vp, f32, f32, f32, f32, f32, _vp,
+                                     _vp, i64, _vp],
+            "brl_mlp_gemm_dh_heads_dw": [i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, i64, _vp, _vp, _vp, i64, i64, i64, i32,
+                                         _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
+        },
+        "brl_sl.h": {   # the supervised pre-trainer's entry points
+            "brl_sl_sample": [i32, _vp, _vp, i64, u64, i64, _vp, _vp, _vp],
+            "brl_sl_replay": [i32, _vp, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp],
+            "brl_sl_loss": [i32, _vp, i64, _vp, _vp, i64, f32, _vp, _vp, _vp, i64, _vp],
+        },
+        "brl_league.h": {   # the batched league evaluation
+            "brl_league_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
+            "brl_league_forward": [i32, _vp, i64, i32, i64, i32, _vp, _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
+        },
+        "brl_boards.h": {   # the board records
+            "brl_board_records": [i32, _vp, i64, _vp, _vp],
+            "brl_board_imp": [i32, _vp, _vp, i64, _vp, _vp],
+            "brl_board_keep_a": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp],
+        },
+        "brl_book.h": {   # the bidding-system book
+            "brl_book_samples": [i32, _vp, i64, _vp, i32, i32, _vp, _vp, _vp],
+            "brl_book_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp],
+        },
+        "brl_par.h": {   # the double-dummy par
+            "brl_par": [i32, _vp, _vp, _vp, i64, _vp, _vp],
+            "brl_par_imp": [i32, _vp, _vp, i64, i32, _vp, _vp],
+        },
+        "brl_review.h": {   # the call review
+            "brl_review_expand": [i32, _vp, _vp, i64, i32, _vp, i64, i64, _vp, _vp, _vp],
+            "brl_review_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp, _vp],
+        },
+        "brl_belief.h": {   # the hand beliefs
+            "brl_belief_deal": [i32, _vp, i64, i64, u64, i64, _vp, _vp, _vp],
+            "brl_belief_logp": [i32, _vp, i64, _vp, i64, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp],
+            "brl_belief_reduce": [i32, _vp, i64, i64, _vp, _vp, _vp, _vp, _vp],
+        },
+        "brl_belief_smc.h": {   # the beliefs' resample-move stages
+            "brl_belief_resample": [i32, _vp, i64, _vp, i64, i64, u64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_belief_propose": [i32, _vp, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp],
+            "brl_belief_accept": [i32, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        },
+        "brl_compare.h": {   # the system diff
+            "brl_compare_tables": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+            "brl_compare_rows": [i32, _vp, i64, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+            "brl_compare_reduce": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
+        },
+        "brl_crossplay.h": {   # cross-play's route
+            "brl_xplay_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
+        },
+        "brl_distill.h": {   # policy distillation's targets and loss head
+            "brl_distill_targets": [i32, _vp, i64, i64, _vp, i64, i64, _vp, _vp, i64, i32, f32, _vp, _vp, _vp, _vp],
+            "brl_distill_loss": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp, _vp],
+        },
+        "brl_lines.h": {   # the auction lines' beam search
+            "brl_lines_init": [i32, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_lines_expand": [i32, _vp, _vp, _vp, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_lines_finish": [i32, _vp, _vp, i64, _vp, _vp],
+            "brl_lines_imp": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, i32, _vp, _vp],
+        },
+        "brl_positions.h": {   # the position queries
+            "brl_position_rows": [i32, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp],
+            "brl_position_answers": [i32, _vp, i64, _vp, i64, _vp, _vp, i64, i32, _vp, _vp, _vp],
+        },
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = ["brl_last_error", *SIGNATURES["brl_hip.h"]]   # every symbol of include/brl_hip.h (brl_last_error returns a string)
 
 _lib = None
 
@@ -92,229 +231,14 @@ def lib() -> C.CDLL:
             "Run `python -m brl_amd.build` (needs hipcc, gfx950). brl_amd has no CPU fallback."
         )
     L = C.CDLL(LIB_PATH)
-    i64, i32, u32, u64, f32 = C.c_int64, C.c_int, C.c_uint32, C.c_uint64, C.c_float
     L.brl_last_error.restype = C.c_char_p
-    L.brl_version.restype = i32
-    sigs = {
-        "brl_create": [i32, _vp, _vp, i64, C.POINTER(_vp)],
-        "brl_set_lut": [_vp, _vp, _vp, i64],
-        "brl_destroy": [_vp],
-        "brl_set_rng": [_vp, u64, u64],
-        "brl_init_random": [_vp, _vp, i64, u32, _vp],
-        "brl_init_from_deals": [_vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_step": [_vp, _vp, _vp, i64, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_observe": [_vp, _vp, i64, _vp, _vp, _vp, _vp],
-        "brl_get_fields": [_vp, _vp, i64, C.POINTER(Fields), _vp],
-        "brl_rollout_random": [_vp, _vp, i64, i32, i32, u32, f32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp],
-        "brl_rollout_random_gae": [_vp, _vp, i64, i32, u32, f32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp, f32, f32, _vp, _vp,
-                                   _vp],
-        "brl_policy_step": [_vp, _vp, _vp, i64, _vp, i32, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_policy_step_at": [_vp, _vp, _vp, i64, _vp, i64, i32, _vp, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_policy_step_ex": [_vp, _vp, _vp, i64, _vp, i64, i32, _vp, u32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                               C.POINTER(MacroExt), _vp],
-        "brl_obs_cast": [_vp, _vp, i64, _vp, i32, _vp],
-        "brl_obs_cast_rows": [_vp, _vp, _vp, i64, _vp, i32, _vp],
-        "brl_live_index": [_vp, _vp, i64, _vp, _vp, i64, _vp],
-        "brl_linear_act_heads": [_vp, _vp, i64, _vp, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, _vp, i64, i32, _vp, i64, i64, _vp],
-        "brl_linear_act": [_vp, _vp, i64, _vp, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, _vp],
-        "brl_gae": [_vp, _vp, _vp, _vp, _vp, f32, f32, i32, i64, _vp, _vp, _vp],
-        "brl_imp_reward": [_vp, _vp, _vp, _vp, i64, _vp],
-        "brl_duplicate_step": [_vp, _vp, _vp, i64, _vp, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
-                               _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_eval_step": [_vp, _vp, _vp, i64, _vp, i64, _vp, i64, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
-                          C.POINTER(EvalStatsPtrs), i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_eval_step_team": [_vp, _vp, _vp, i64, _vp, i64, i32, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs),
-                               C.POINTER(EvalStatsPtrs), i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_eval_reduce": [_vp, i64, C.POINTER(TableInfoPtrs), C.POINTER(TableInfoPtrs), _vp, _vp, _vp, _vp],
-        "brl_ppo_loss": [i32, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, _vp, _vp, _vp, _vp, _vp],
-        "brl_ppo_stats": [i32, _vp, i64, _vp, f32, f32, _vp, _vp],
-        "brl_ppo_heads_loss_split": [i32, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, i32, _vp, _vp, _vp, _vp, _vp, i32, _vp],
-        "brl_ppo_heads_bwd": [i32, _vp, _vp, i64, _vp, i64, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
-        "brl_ppo_stats_rows": [i32, _vp, _vp, i64, i64, f32, f32, f32, _vp, _vp],
-        "brl_mb_gather_bind": [i32, C.POINTER(TransitionPtrs), _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp, _vp],
-        "brl_adam_clip_fin_gather": [i32, _vp, _vp, _vp, _vp, i64, _vp, f32, _vp, f32, f32, f32, f32, _vp, i64, _vp, _vp, _vp, i64,
-                                     i32, _vp, _vp, _vp, _vp, _vp],
-        "brl_mb_gather_dev": [i32, _vp, i64, _vp],
-        "brl_ppo_stats_gram": [i32, _vp, i64, i64, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp],
-        "brl_ppo_illegal_grad": [i32, _vp, _vp, _vp, f32, i64, _vp, _vp],
-        "brl_act_bwd_colsum": [i32, _vp, _vp, i64, i64, i64, i32, _vp, _vp],
-        "brl_act_bwd_colsum_heads_dw": [i32, _vp, _vp, i64, i64, i64, i32, _vp, _vp, _vp, i64, i64, i64, i32, _vp, _vp, _vp, _vp, i64,
-                                        _vp, _vp, _vp, _vp],
-        "brl_bias_finalize_ex": [i32, i32, _vp, _vp, _vp, _vp, _vp],
-        "brl_bias_finalize_rows": [i32, i32, _vp, _vp, _vp, _vp, i32, _vp, _vp],
-        "brl_fair_forward": [i32, C.POINTER(FairNet), _vp, i64, i32, _vp, _vp, _vp],
-        "brl_mlp_gemm_group": [i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_fair_chain": [i32, C.POINTER(FairNet), _vp, _vp, _vp, _vp, _vp, _vp, _vp, i64, f32, f32, f32, i32, i32, i32, i32,
-                           C.POINTER(FairWork), _vp],
-        "brl_mlp_gemm": [i32, i32, i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, _vp, i64, _vp, _vp, _vp],
-        "brl_mlp_gemm_x3_workspace": [i64, i64, i64, _vp],
-        "brl_mlp_gemm_x3_group": [i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_split_planes": [i32, _vp, i64, _vp, i64, _vp],
-        "brl_linear_x3p": [i32, _vp, i32, i64, i64, _vp, i64, i64, _vp, i32, _vp, i64, _vp, i64, i64, i64, i64, i64, _vp],
-        "brl_mlp_gemm_x3": [i32, i32, i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, _vp, i64, _vp, _vp, i64, _vp],
-        "brl_mlp_forward_rows": [i32, C.POINTER(MlpRef), _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
-        "brl_adam_shard_norm": [i32, _vp, C.POINTER(ShardGeom), i32, i32, f32, _vp, _vp, _vp, _vp],
-        "brl_adam_shard_apply": [i32, _vp, _vp, _vp, _vp, C.POINTER(ShardGeom), i32, i32, _vp, _vp, f32, _vp, f32, f32, f32, f32, f32, _vp,
-                                 _vp, i64, _vp],
-        "brl_mlp_gemm_dh_heads_dw": [i32, _vp, i64, _vp, i64, _vp, i64, i64, i64, i64, i32, _vp, i64, _vp, _vp, _vp, i64, i64, i64, i32,
-                                     _vp, _vp, _vp, _vp, i64, _vp, _vp, _vp, _vp],
-    }
-    sigs.update(sl_signatures())
-    sigs.update(league_signatures())
-    sigs.update(boards_signatures())
-    sigs.update(book_argtypes())
-    sigs.update(par_argtypes())
-    sigs.update(review_argtypes())
-    sigs.update(belief_argtypes())
-    sigs.update(belief_smc_argtypes())
-    sigs.update(compare_argtypes())
-    sigs.update(crossplay_argtypes())
-    sigs.update(distill_argtypes())
-    sigs.update(lines_argtypes())
-    sigs.update(positions_argtypes())
-    for name, args in sigs.items():
-        fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = i32
+    for sigs in SIGNATURES.values():
+        for name, args in sigs.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
     _lib = L
     return L
-
-
-EXPORTS = ["brl_last_error", "brl_version", "brl_create", "brl_set_lut", "brl_destroy", "brl_set_rng",
-           "brl_init_random", "brl_init_from_deals", "brl_step", "brl_observe", "brl_get_fields",
-           "brl_rollout_random", "brl_policy_step", "brl_policy_step_at", "brl_obs_cast", "brl_obs_cast_rows", "brl_live_index", "brl_linear_act", "brl_linear_act_heads", "brl_gae", "brl_imp_reward", "brl_duplicate_step",
-           "brl_eval_step", "brl_eval_reduce", "brl_ppo_loss", "brl_ppo_stats", "brl_policy_step_ex",
-           "brl_eval_step_team", "brl_rollout_random_gae", "brl_ppo_heads_loss_split", "brl_adam_shard_norm", "brl_adam_shard_apply", "brl_ppo_heads_bwd", "brl_ppo_stats_gram",
-           "brl_act_bwd_colsum", "brl_act_bwd_colsum_heads_dw", "brl_bias_finalize_ex", "brl_ppo_stats_rows", "brl_mb_gather_bind", "brl_mb_gather_dev", "brl_ppo_illegal_grad", "brl_adam_clip_fin_gather", "brl_mlp_gemm", "brl_mlp_gemm_dh_heads_dw", "brl_mlp_forward_rows",
-           "brl_bias_finalize_rows", "brl_fair_chain", "brl_mlp_gemm_group", "brl_fair_forward", "brl_mlp_gemm_x3", "brl_mlp_gemm_x3_workspace", "brl_mlp_gemm_x3_group", "brl_split_planes", "brl_linear_x3p"]
-
-
-def sl_signatures() -> dict:
-    """argtypes of include/brl_sl.h (the supervised pre-trainer's entry points; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32, u64, f32 = C.c_int64, C.c_int, C.c_uint64, C.c_float
-    return {
-        "brl_sl_sample": [i32, _vp, _vp, i64, u64, i64, _vp, _vp, _vp],
-        "brl_sl_replay": [i32, _vp, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp, _vp],
-        "brl_sl_loss": [i32, _vp, i64, _vp, _vp, i64, f32, _vp, _vp, _vp, i64, _vp],
-    }
-
-
-class LeagueNet(C.Structure):
-    """brl_league_net (include/brl_league.h): one "DeepMind" fp32 network by reference, 20 device pointers"""
-    _fields_ = [("w", _vp * 8), ("b", _vp * 8), ("actor_w", _vp), ("actor_b", _vp), ("critic_w", _vp), ("critic_b", _vp)]
-
-
-def league_signatures() -> dict:
-    """argtypes of include/brl_league.h (the batched league evaluation; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_league_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
-        "brl_league_forward": [i32, _vp, i64, i32, i64, i32, _vp, _vp, _vp, i64, _vp, i64, _vp, i64, _vp],
-    }
-
-
-def boards_signatures() -> dict:
-    """argtypes of include/brl_boards.h (the board records; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_board_records": [i32, _vp, i64, _vp, _vp],
-        "brl_board_imp": [i32, _vp, _vp, i64, _vp, _vp],
-        "brl_board_keep_a": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp],
-    }
-
-
-def book_argtypes() -> dict:
-    """argtypes of include/brl_book.h (the bidding-system book; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_book_samples": [i32, _vp, i64, _vp, i32, i32, _vp, _vp, _vp],
-        "brl_book_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp],
-    }
-
-
-def par_argtypes() -> dict:
-    """argtypes of include/brl_par.h (the double-dummy par; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_par": [i32, _vp, _vp, _vp, i64, _vp, _vp],
-        "brl_par_imp": [i32, _vp, _vp, i64, i32, _vp, _vp],
-    }
-
-
-def review_argtypes() -> dict:
-    """argtypes of include/brl_review.h (the call review; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_review_expand": [i32, _vp, _vp, i64, i32, _vp, i64, i64, _vp, _vp, _vp],
-        "brl_review_reduce": [i32, _vp, _vp, i64, _vp, i64, _vp, _vp, _vp],
-    }
-
-
-def belief_argtypes() -> dict:
-    """argtypes of include/brl_belief.h (the hand beliefs; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32, u64 = C.c_int64, C.c_int, C.c_uint64
-    return {
-        "brl_belief_deal": [i32, _vp, i64, i64, u64, i64, _vp, _vp, _vp],
-        "brl_belief_logp": [i32, _vp, i64, _vp, i64, _vp, i64, _vp, _vp, i64, _vp, _vp, _vp],
-        "brl_belief_reduce": [i32, _vp, i64, i64, _vp, _vp, _vp, _vp, _vp],
-    }
-
-
-def belief_smc_argtypes() -> dict:
-    """argtypes of include/brl_belief_smc.h (the beliefs' resample-move stages; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32, u64 = C.c_int64, C.c_int, C.c_uint64
-    return {
-        "brl_belief_resample": [i32, _vp, i64, _vp, i64, i64, u64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_belief_propose": [i32, _vp, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp],
-        "brl_belief_accept": [i32, _vp, i64, _vp, i64, i64, u64, i64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    }
-
-
-def compare_argtypes() -> dict:
-    """argtypes of include/brl_compare.h (the system diff; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_compare_tables": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
-        "brl_compare_rows": [i32, _vp, i64, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
-        "brl_compare_reduce": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp],
-    }
-
-
-def crossplay_argtypes() -> dict:
-    """argtypes of include/brl_crossplay.h (cross-play's route; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_xplay_route": [i32, _vp, _vp, i32, i64, _vp, _vp, i64, i64, _vp, _vp, _vp, _vp],
-    }
-
-
-def distill_argtypes() -> dict:
-    """argtypes of include/brl_distill.h (policy distillation's targets and loss head; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32, f32 = C.c_int64, C.c_int, C.c_float
-    return {
-        "brl_distill_targets": [i32, _vp, i64, i64, _vp, i64, i64, _vp, _vp, i64, i32, f32, _vp, _vp, _vp, _vp],
-        "brl_distill_loss": [i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, i64, f32, f32, f32, _vp, _vp, _vp, _vp, _vp],
-    }
-
-
-def lines_argtypes() -> dict:
-    """argtypes of include/brl_lines.h (the auction lines' beam search; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_lines_init": [i32, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_lines_expand": [i32, _vp, _vp, _vp, _vp, i64, i32, i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_lines_finish": [i32, _vp, _vp, i64, _vp, _vp],
-        "brl_lines_imp": [i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, i32, _vp, _vp],
-    }
-
-
-def positions_argtypes() -> dict:
-    """argtypes of include/brl_positions.h (the position queries; not part of brl_hip.h nor of EXPORTS)"""
-    i64, i32 = C.c_int64, C.c_int
-    return {
-        "brl_position_rows": [i32, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp],
-        "brl_position_answers": [i32, _vp, i64, _vp, i64, _vp, _vp, i64, i32, _vp, _vp, _vp],
-    }
 
 
 def check(rc: int) -> None:

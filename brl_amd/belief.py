@@ -433,11 +433,11 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
     "logl" float32 [K]; the ``HandBelief`` carries ``resamples``, ``proposals``, ``accepted`` and ``distinct``.  R = 0 (the
     default) is the plain path: the same launches, the same bytes."""
     import torch
-    import torch.distributed as dist
 
     from . import _capi
     from ._capi import OBS_SIZE
-    from .evaluation import _team_forwards
+    from .dist import one_rank_only
+    from .evaluation import _Forward, _team_forwards
     from .models import make_forward_pass
     fp1 = make_forward_pass(team1_activation, team1_model_type)
     fp2 = make_forward_pass(team2_activation, team2_model_type)
@@ -453,11 +453,8 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
         """logits of one query's K observation rows.  A query's rows always go through the network as one batch of exactly K rows:
         which kernels a forward runs on, and with them the last bits of a logit, depend on the batch's size, so a batch made of
         whatever queries happen to be processed together would make the entries depend on the grouping."""
-        dtype, fmt = fwd.cast(K)
-        x = torch.empty((K, OBS_SIZE), dtype=dtype, device=obs.device)
-        _capi.check(_capi.lib().brl_obs_cast(eval_env._h, obs.data_ptr(), K, _capi.ptr(x), fmt, _capi.stream()))
-        out = fwd(None, x)
-        return out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
+        assert obs.shape[0] == K
+        return _Forward.whole(fwd, obs, eval_env)
 
     def batch(fwds, qs, plans, q_index, rows, counts):
         """the entries of the queries ``qs`` (already ordered by falling prefix length), stream indices ``q_index``, and with
@@ -588,8 +585,7 @@ def make_hand_belief(eval_env, team1_activation, team1_model_type, team2_activat
                          "distinct": np.array([len(np.unique(h[i], axis=0)) for i in range(Q)], np.int64)}
 
     def hand_belief(team1_params, team2_params, queries, query_offset: int = 0, rows=None, counts=None):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("hand_belief runs on one rank (a process group is up): call it on one rank only, outside the group")
+        one_rank_only("hand_belief")
         queries = list(queries)
         plans = [q.plan(i) for i, q in enumerate(queries)]          # refuses an illegal prefix before anything is sampled
         if not queries:

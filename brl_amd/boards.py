@@ -475,8 +475,8 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
 
     Table A's final states are kept by ``_KeepA``, one launch behind every step.  Runs on one rank."""
     import torch
-    import torch.distributed as dist
 
+    from .dist import one_rank_only
     from .duplicate import Table_info
     from .evaluation import _eval_loop, _match_stats, _team_forwards
     from .models import make_forward_pass
@@ -484,8 +484,7 @@ def make_board_match(eval_env, team1_activation, team1_model_type, team2_activat
     fp2 = make_forward_pass(team2_activation, team2_model_type)
 
     def board_match(team1_params, team2_params, deals_or_key):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("board_match runs on one rank (a process group is up): call it on one rank only, outside the group")
+        one_rank_only("board_match")
         dev = eval_env.device
         with torch.no_grad():
             if isinstance(deals_or_key, Deals):

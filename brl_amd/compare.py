@@ -318,22 +318,15 @@ def make_policy_diff(eval_env, x_activation, x_model_type, y_activation, y_model
         raise ValueError("max_rows >= 1")
     depth, max_rows = int(depth), int(max_rows)
     import torch
-    import torch.distributed as dist
 
     from . import _capi
     from ._capi import OBS_SIZE
-    from .evaluation import _team_forwards
+    from .dist import one_rank_only
+    from .evaluation import _Forward, _team_forwards
     from .models import make_forward_pass
     fpx = make_forward_pass(x_activation, x_model_type)
     fpy = make_forward_pass(y_activation, y_model_type)
     off = lambda name: RECORD_DTYPE.fields[name][1]     # noqa: E731
-
-    def forward(fwd, obs, m):
-        dtype, fmt = fwd.cast(m)
-        x = torch.empty((m, OBS_SIZE), dtype=dtype, device=obs.device)
-        _capi.check(_capi.lib().brl_obs_cast(eval_env._h, obs.data_ptr(), m, _capi.ptr(x), fmt, _capi.stream()))
-        out = fwd(None, x)
-        return out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
 
     def chunk(fwdx, fwdy, rec, decisions, taken, label):
         """the decisions of the records ``rec`` into ``decisions`` (zeroed, uint8 [n * depth, 64]); -> the records skipped (a tensor)"""
@@ -358,8 +351,7 @@ def make_policy_diff(eval_env, x_activation, x_model_type, y_activation, y_model
             mask = torch.empty((m, ACTIONS), dtype=torch.uint8, device=dev)
             _capi.check(L.brl_observe(eval_env._h, _capi.ptr(tables), m, None, _capi.ptr(obs), _capi.ptr(mask), _capi.stream()))
             legal = (mask.to(torch.int64) * bit[None, :]).sum(1)
-            lx = forward(fwdx, obs, m)
-            ly = lx if fwdy is fwdx else forward(fwdy, obs, m)
+            lx, ly = _Forward.whole_pair(fwdx, fwdy, obs, eval_env)
             compare_rows(rec, rows_[:m], t, depth, lx, ly, legal, decisions)
             if taken is not None:
                 taken.append(dict(label, t=t, rows=rows_[:m], logits_x=lx[:, :ACTIONS].clone(), logits_y=ly[:, :ACTIONS].clone(), legal=legal))
@@ -368,8 +360,7 @@ def make_policy_diff(eval_env, x_activation, x_model_type, y_activation, y_model
         return (~ok).sum()
 
     def policy_diff(x_params, y_params, records, tables="ab", rows=None):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("policy_diff runs on one rank (a process group is up): call it on one rank only, outside the group")
+        one_rank_only("policy_diff")
         if tables not in ("a", "b", "ab"):
             raise ValueError(f"tables={tables!r}: 'a', 'b' or 'ab'")
         if isinstance(records, BoardRecords):

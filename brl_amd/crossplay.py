@@ -150,6 +150,7 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
     is true.  ``boards=True``: additionally returns one ``BoardRecords`` per line-up (both tables, IMP, ``dda``) — what
     ``system_book(records)`` reads to show what a call means in THAT partnership.  Runs on one rank."""
     from .boards import _KeepA
+    from .dist import one_rank_only
     from .duplicate import Table_info
     from .evaluation import _DoneWatch, _Forward
     from .models import make_forward_pass
@@ -185,10 +186,9 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
                     break
                 t = i & 1
                 fa, fb = fwds[int(lu[2 * t])], fwds[int(lu[2 * t + 1])]
-                x = obs.to(torch.float32)
-                lg = fa(obs, x)
+                lg, lb = _Forward.whole_pair(fa, fb, obs)
                 if fb is not fa:   # the half decides whose logits a board takes
-                    lg = torch.where((cur & 1)[:, None] == 0, lg[:, :NUM_ACTIONS], fb(obs, x)[:, :NUM_ACTIONS])
+                    lg = torch.where((cur & 1)[:, None] == 0, lg[:, :NUM_ACTIONS], lb[:, :NUM_ACTIONS])
                 lg = lg.contiguous()
                 if rec is not None and record.get("logits"):
                     rec["logits"].append(lg[:, :NUM_ACTIONS].clone())
@@ -207,9 +207,7 @@ def make_lineup_evaluate(eval_env, activation, model_type, num_eval_envs, max_bo
                 out_records.extend(keep.records("lineup_evaluate", dda, cum[p:p + 1], n))
 
     def lineup_evaluate(params_list, lineups, rng_key):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("lineup_evaluate runs on one rank (a process group is up): call it on one rank only")
+        one_rank_only("lineup_evaluate")
         lineups = _lineups(lineups)
         if len(lineups) and (lineups.min() < 0 or lineups.max() >= len(params_list)):
             raise ValueError("lineups name a network outside params_list")

@@ -15,6 +15,14 @@ def distributed() -> bool:
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("BRL_FORCE_DIST") == "1")
 
 
+def one_rank_only(tool: str) -> None:
+    """the refusal of a tool that runs on one rank: raises where a process group of more than one rank is up (the world size alone:
+    the BRL_FORCE_DIST rehearsal at world 1 is one rank)"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise RuntimeError(f"{tool} runs on one rank (a process group is up): call it on one rank only, outside the group")
+
+
 def rank_world():
     return int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
 

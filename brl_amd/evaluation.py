@@ -86,7 +86,8 @@ class _Forward:
     """logits of one team's network for a batch of observations: the fused inference snapshot when the architecture is covered
     (DeepMind / ReLU), else the module itself.  Returns a float32 [n, >=38] matrix whose first 38 columns are the logits (row stride
     may be 39: merged actor + critic heads).  It owns the question "what does this forward take as input, and on which rows":
-    ``route`` for the loops, ``cast`` for a caller that casts the observation itself.  A CONSTANT forward — the same logits whatever
+    ``route`` decides, ``whole`` runs a forward on every row (the loops and the analysis tools alike), ``cast`` names the input of the
+    loops' forwards on an index list.  A CONSTANT forward — the same logits whatever
     the observation (``_PassOnly``, the tests' scripted doubles) — is any object with a ``constant = True`` class attribute and
     ``__call__(obs_bool, obs_f32)``."""
     constant = False
@@ -115,6 +116,42 @@ class _Forward:
         if m <= _OWN_FORWARD_ROWS and fwd.ref is not None:
             return "rows_own"    # brl_mlp_forward_rows: the iteration is bound by host launches
         return "rows_bf16" if fwd._planes(m) else "rows_f32"   # brl_obs_cast_rows (gather + astype), the forward, index_copy_
+
+    @staticmethod
+    def _f32(obs, env):   # the bool rows as float32: brl_obs_cast through the environment's handle, torch's own cast without one
+        return obs.to(torch.float32) if env is None else _Forward._obs_cast(obs, env, torch.float32, 0)
+
+    @staticmethod
+    def _obs_cast(obs, env, dtype, fmt):   # one brl_obs_cast launch: the 0/1 rows in ``dtype`` (format code ``fmt``: see ``cast``)
+        x = torch.empty(obs.shape, dtype=dtype, device=obs.device)
+        check(_capi.lib().brl_obs_cast(env._h, ptr(obs), obs.shape[0], ptr(x), fmt, stream()))
+        return x
+
+    @staticmethod
+    def whole(fwd, obs, env=None, x=None):
+        """the logits of ``fwd`` (a ``_Forward`` or a constant forward) for EVERY row of ``obs`` (bool [m, 480]): float32 [m, >= 38]
+        with unit column stride.  ``route(fwd, m, False)`` alone decides the input: "constant" and "full_bool" take the bool rows,
+        "full_f32" takes ``x`` (the rows as float32, where a step launch wrote them already), else ``_f32(obs, env)``; nothing is
+        cast that the route does not read.  With an environment "full_bool" hands the snapshot the one bf16 plane it reads as
+        ``brl_obs_cast`` writes it (the snapshot's own cast of the bool rows is torch's: the same plane from a slower kernel)."""
+        route = _Forward.route(fwd, obs.shape[0], False)
+        if route == "full_f32":
+            out = fwd(obs, x if x is not None else _Forward._f32(obs, env))
+        elif route == "full_bool" and env is not None:
+            out = fwd(None, _Forward._obs_cast(obs, env, *fwd.cast(obs.shape[0])))
+        else:
+            out = fwd(obs, None)
+        return out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
+
+    @staticmethod
+    def whole_pair(fwd1, fwd2, obs, env=None):
+        """``whole`` of two teams' forwards on the same rows: ONE result where they are one object, one cast where both read float32"""
+        if fwd2 is fwd1:
+            return (_Forward.whole(fwd1, obs, env),) * 2
+        x = None
+        if all(_Forward.route(f, obs.shape[0], False) == "full_f32" for f in (fwd1, fwd2)):
+            x = _Forward._f32(obs, env)
+        return _Forward.whole(fwd1, obs, env, x), _Forward.whole(fwd2, obs, env, x)
 
     @staticmethod
     def _by_reference(m):
@@ -341,7 +378,7 @@ class _ActiveRows:
         if route == "constant":
             return fwd(obs, None)
         if not shrunk:
-            self.full = fwd(obs, None) if route == "full_bool" else fwd(obs, x if x is not None else obs.to(torch.float32))
+            self.full = _Forward.whole(fwd, obs, x=x)
             if fwd.ref is not None and self.full.stride(0) <= NUM_ACTIONS:
                 # (the module's own [n, 38] logits: brl_mlp_forward_rows writes 38 + 1 numbers per row later on)
                 wide = torch.empty((self.full.shape[0], NUM_ACTIONS + 2), dtype=torch.float32, device=self.full.device)
@@ -412,9 +449,7 @@ def _eval_loop(env: BridgeBidding, state: State, fwd1: _Forward, fwd2: _Forward,
                 rows[0].update(polled)
                 l1 = l2 = rows[0].forward(fwd1, obs, env)
             else:
-                x = obs.to(torch.float32)
-                l1 = fwd1(obs, x)
-                l2 = fwd2(obs, x) if fwd2 is not fwd1 else l1   # G10: the reference evaluates both networks and selects
+                l1, l2 = _Forward.whole_pair(fwd1, fwd2, obs)   # G10: the reference evaluates both networks and selects
             if logits is not None:
                 team1 = (State(env, packed).current_player < 2)[:, None]
                 logits.append(torch.where(team1, l1[:, :NUM_ACTIONS], l2[:, :NUM_ACTIONS]).clone())

@@ -302,17 +302,6 @@ def swapped_seating(packed):
     return out
 
 
-def _logits(fwd, obs):
-    """float32 [rows, >= 38] of one network for every row of ``obs``, through ``_Forward``'s own route for that many rows"""
-    import torch
-
-    from .evaluation import _Forward
-    route = _Forward.route(fwd, obs.shape[0], False)
-    if route in ("constant", "full_bool"):
-        return fwd(obs, None)
-    return fwd(obs, obs.to(torch.float32))
-
-
 def search(env, packed, fwd1, fwd2, k, max_calls, record=None):
     """the beam search of one table's dealt tables ``packed``: (final ``Beam``, steps run, rows forwarded per step).  Every step
     observes the lines' tables, forwards every row through the networks (ONE forward when ``fwd2 is fwd1``) and expands.  The loop
@@ -321,7 +310,7 @@ def search(env, packed, fwd1, fwd2, k, max_calls, record=None):
     nothing).  ``record``: a list that receives {"beam": step 0's beam} and then per step {"logits1", "logits2" float32 [n*K,38],
     "obs" bool [n*K,480], "mask" bool [n*K,38], "request": the requests of the beam the step read, "beam": the beam after the step}
     as host arrays."""
-    from .evaluation import _DoneWatch
+    from .evaluation import _DoneWatch, _Forward
     n = packed.shape[0]
     beam = lines_init(packed, k, max_calls)
     spare = Beam(n, beam.k, beam.max_calls, packed.device)
@@ -336,8 +325,7 @@ def search(env, packed, fwd1, fwd2, k, max_calls, record=None):
             if polled is not None and polled[0] >= n:
                 break
             obs, mask = env._observe_raw(beam.tables, None)
-            l1 = _logits(fwd1, obs)
-            l2 = l1 if fwd2 is fwd1 else _logits(fwd2, obs)
+            l1, l2 = _Forward.whole_pair(fwd1, fwd2, obs)
             nxt = lines_expand(beam, l1, l2, spare)
             if record is not None:
                 record.append({"logits1": l1[:, :38].cpu().numpy(), "logits2": l2[:, :38].cpu().numpy(), "obs": obs.cpu().numpy(),
@@ -361,9 +349,9 @@ def make_auction_lines(eval_env, team1_activation, team1_model_type, team2_activ
     receives, per table, the list ``search`` fills.  The result has ``steps`` = (table A's, table B's) and ``rows_per_step``.
     Runs on one rank."""
     import torch
-    import torch.distributed as dist
 
     from .boards import Deals
+    from .dist import one_rank_only
     from .evaluation import _team_forwards
     from .models import make_forward_pass
     _check_beam(k, max_calls)
@@ -371,8 +359,7 @@ def make_auction_lines(eval_env, team1_activation, team1_model_type, team2_activ
     fp2 = make_forward_pass(team2_activation, team2_model_type)
 
     def auction_lines(team1_params, team2_params, deals_or_key):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("auction_lines runs on one rank (a process group is up): call it on one rank only, outside the group")
+        one_rank_only("auction_lines")
         with torch.no_grad():
             if isinstance(deals_or_key, Deals):
                 d = deals_or_key

@@ -308,12 +308,10 @@ def _heads(fwd, obs):
     import torch
 
     from .evaluation import _Forward
-    route = _Forward.route(fwd, obs.shape[0], False)
-    if route != "constant" and fwd.snap is None:
+    if not fwd.constant and fwd.snap is None:
         logits, value = fwd.fp.apply(fwd.params, obs.to(torch.float32))
         return logits.float().contiguous(), value.reshape(-1).float().contiguous()
-    out = fwd(obs, None) if route in ("constant", "full_bool") else fwd(obs, obs.to(torch.float32))
-    out = out if out.dtype == torch.float32 and out.stride(1) == 1 else out.float().contiguous()
+    out = _Forward.whole(fwd, obs)
     return out, (out[:, ACTIONS] if out.shape[1] > ACTIONS else None)
 
 

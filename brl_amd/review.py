@@ -219,10 +219,10 @@ def make_call_review(eval_env, team1_activation, team1_model_type, team2_activat
     The value of an action is hindsight on the actual deal under the policies' own greedy continuations, scored against the
     recorded result of the other table; it is not a double-dummy judgement of the call."""
     import torch
-    import torch.distributed as dist
 
     from .boards import board_records
     from .bridge_bidding import State
+    from .dist import one_rank_only
     from .evaluation import _eval_loop, _team_forwards
     from .models import make_forward_pass
     fp1 = make_forward_pass(team1_activation, team1_model_type)
@@ -232,8 +232,7 @@ def make_call_review(eval_env, team1_activation, team1_model_type, team2_activat
     per = int(max_branches) // ACTIONS
 
     def call_review(team1_params, team2_params, records, tables="ab", record=None):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise RuntimeError("call_review runs on one rank (a process group is up): call it on one rank only, outside the group")
+        one_rank_only("call_review")
         if records.dda is None:
             raise ValueError("call_review: the records hold no double-dummy tables (dda=)")
         if records.table_b is None:

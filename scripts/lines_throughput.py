@@ -82,10 +82,10 @@ def kernels(nets, k):
     beam = lines.lines_init(state.packed, k, lines.MAX_CALLS)
     for _ in range(5):
         obs, _ = env._observe_raw(beam.tables, None)
-        l1, l2 = lines._logits(fwd1, obs), lines._logits(fwd2, obs)
+        l1, l2 = evaluation._Forward.whole_pair(fwd1, fwd2, obs)
         beam = lines.lines_expand(beam, l1, l2)
     obs, _ = env._observe_raw(beam.tables, None)
-    l1, l2 = lines._logits(fwd1, obs), lines._logits(fwd2, obs)
+    l1, l2 = evaluation._Forward.whole_pair(fwd1, fwd2, obs)
     spare = lines.Beam(N, k, lines.MAX_CALLS, DEV)
     us, runs = launches(lambda: lines.lines_expand(beam, l1, l2, spare))
     live = int(((beam.flags & (lines.EMPTY | lines.FINISHED | lines.VOID)) == 0).sum())

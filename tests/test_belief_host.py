@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-from brl_amd import _capi, belief, boards
+from brl_amd import belief, boards
 from tests import belief_ref as BR
 from tests import board_records_ref as R
 from tests import book_ref as B
@@ -29,12 +29,6 @@ def _entry(d):
 # ---- the header and the binding -------------------------------------------------------------------------------------------------
 def test_the_header_states_what_the_binding_and_the_host_read():
     text = open(os.path.join(ROOT, "include", "brl_belief.h")).read()
-    names = sorted(set(re.findall(r"\bint (brl_belief_\w+)\(", text)))
-    assert names == sorted(_capi.belief_argtypes()) == ["brl_belief_deal", "brl_belief_logp", "brl_belief_reduce"]
-    assert not set(_capi.belief_argtypes()) & set(_capi.EXPORTS)
-    for name, args in _capi.belief_argtypes().items():      # one argtype per parameter of the prototype
-        proto = re.search(r"\bint " + name + r"\((.*?)\);", text, re.S).group(1)
-        assert len(args) == proto.count(",") + 1, name
     assert f"#define BRL_BELIEF_ACTIONS {belief.ACTIONS}\n" in text and f"#define BRL_BELIEF_STREAM 0x{belief.STREAM:08X}u" in text
     assert f"#define BRL_BELIEF_ENTRY_BYTES {belief.ENTRY_DTYPE.itemsize}\n" in text and belief.QUERY_DTYPE.itemsize == 16
     assert (BR.STREAM, BR.HIDDEN) == (belief.STREAM, 39)

@@ -2,6 +2,7 @@
 that include/brl_hip.h declares; the host mirror keeps the reference's names; there is no
 fallback path when the extension or the GPU is missing.  No compute calls (no GPU here)."""
 import ctypes
+import glob
 import os
 import re
 
@@ -44,22 +45,64 @@ def test_binding_covers_every_declared_symbol(built_lib):
     assert L.brl_last_error() is not None
 
 
-def test_binding_argument_types_match_header(built_lib):
-    """Every argument of every declaration in include/brl_hip.h against the ctypes argtypes: beyond the sixth integer argument
-    the x86-64 ABI passes on the stack, where an `int` bound to an `int64_t` parameter reads 32 bits of garbage."""
-    from brl_amd import _capi
-    text = open(os.path.join(ROOT, "include", "brl_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
+
+# every `int brl_*(` entry point of every header, spelled out: a new one cannot arrive unnoticed (brl_hip.h's are _capi.EXPORTS, held
+# against the header above)
+ENTRY_POINTS = {
+    "brl_belief.h": ["brl_belief_deal", "brl_belief_logp", "brl_belief_reduce"],
+    "brl_belief_smc.h": ["brl_belief_accept", "brl_belief_propose", "brl_belief_resample"],
+    "brl_boards.h": ["brl_board_imp", "brl_board_keep_a", "brl_board_records"],
+    "brl_book.h": ["brl_book_reduce", "brl_book_samples"],
+    "brl_compare.h": ["brl_compare_reduce", "brl_compare_rows", "brl_compare_tables"],
+    "brl_crossplay.h": ["brl_xplay_route"],
+    "brl_distill.h": ["brl_distill_loss", "brl_distill_targets"],
+    "brl_league.h": ["brl_league_forward", "brl_league_route"],
+    "brl_lines.h": ["brl_lines_expand", "brl_lines_finish", "brl_lines_imp", "brl_lines_init"],
+    "brl_par.h": ["brl_par", "brl_par_imp"],
+    "brl_positions.h": ["brl_position_answers", "brl_position_rows"],
+    "brl_review.h": ["brl_review_expand", "brl_review_reduce"],
+    "brl_sl.h": ["brl_sl_loss", "brl_sl_replay", "brl_sl_sample"],
+}
+
+
+def prototypes(path):
+    """[(return type, name, [kind of every parameter])] of every brl_* prototype of a header; kind: "ptr", 4 / 8 (bytes of an
+    integer), "f", "d".  A parameter type it does not know is a KeyError, not a guess."""
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
-    decls = re.findall(r"\b(?:int|const char \*|void)\s*(brl_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-    assert sorted(n for n, _ in decls) == header_symbols()
     scalar = {"int": 4, "int32_t": 4, "uint32_t": 4, "unsigned": 4, "int64_t": 8, "uint64_t": 8, "float": "f", "double": "d"}
 
-    def c_kind(arg):
+    def kind(arg):
         if "*" in arg:
             return "ptr"
         words = arg.split()
         return scalar[" ".join(words[:-1]) if len(words) > 1 else words[0]]
+    decls = re.findall(r"\b(int|const char \*|void)\s*(brl_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
+    return [(ret, name, [] if args.strip() in ("", "void") else [kind(a.strip()) for a in args.split(",")]) for ret, name, args in decls]
+
+
+def test_the_headers_are_the_ones_the_table_names():
+    from brl_amd import _capi
+    assert [os.path.basename(p) for p in HEADERS] == sorted(_capi.SIGNATURES) == sorted(["brl_hip.h", *ENTRY_POINTS])
+
+
+@pytest.mark.parametrize("header", [os.path.basename(p) for p in HEADERS])
+def test_binding_argument_types_match_header(built_lib, header):
+    """Every argument of every declaration of every header of include/ against the ctypes argtypes of _capi.SIGNATURES[header]:
+    beyond the sixth integer argument the x86-64 ABI passes on the stack, where an `int` bound to an `int64_t` parameter reads
+    32 bits of garbage.  The header's `int brl_*(` prototypes are the table's entry, name for name, and no other header's."""
+    from brl_amd import _capi
+    table = _capi.SIGNATURES[header]
+    decls = prototypes(os.path.join(ROOT, "include", header))
+    if header == "brl_hip.h":
+        assert sorted(n for _, n, _ in decls) == header_symbols() == sorted(_capi.EXPORTS)
+        assert [d for d in decls if d[0] != "int"] == [("const char *", "brl_last_error", [])]
+    else:
+        assert sorted(n for _, n, _ in decls) == ENTRY_POINTS[header] and all(ret == "int" for ret, _, _ in decls)
+    assert sorted(n for ret, n, _ in decls if ret == "int") == sorted(table)
+    for other, sigs in _capi.SIGNATURES.items():
+        assert other == header or not set(sigs) & set(table), f"{sorted(set(sigs) & set(table))} under {header} and {other}"
 
     def py_kind(t):
         if t in (ctypes.c_float,):
@@ -71,10 +114,11 @@ def test_binding_argument_types_match_header(built_lib):
         return ctypes.sizeof(t)
 
     L = _capi.lib()
-    for name, args in decls:
-        want = [] if args.strip() in ("", "void") else [c_kind(a.strip()) for a in args.split(",")]
-        got = [py_kind(t) for t in (getattr(L, name).argtypes or [])]
-        assert want == got, f"{name}: header {want} != ctypes {got}"
+    for ret, name, want in decls:
+        if ret == "int":
+            assert want == [py_kind(t) for t in table[name]], f"{name}: header {want} != table"
+            assert getattr(L, name).argtypes == table[name] and getattr(L, name).restype is ctypes.c_int, name
+        assert want == [py_kind(t) for t in (getattr(L, name).argtypes or [])], f"{name}: header {want} != ctypes"
 
 
 def test_struct_layouts_match_header():

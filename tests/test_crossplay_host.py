@@ -1,10 +1,8 @@
 """CPU checks of cross-play's host side (brl_amd/crossplay.py, include/brl_crossplay.h): the header against the ctypes binding, the
 per-team slot orders, the route's numpy restatement on hand-made cases (tests/crossplay_ref.py: what tests/test_gpu_crossplay.py
 compares the kernels with), the CrossPlay arithmetic against a by-hand float64 restatement, and the CLI's parser."""
-import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,15 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_the_header_is_the_binding():
     from brl_amd import _capi
-    text = open(os.path.join(ROOT, "include", "brl_crossplay.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decls = re.findall(r"\bint\s+(brl_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-    sigs = _capi.crossplay_argtypes()
-    assert [n for n, _ in decls] == ["brl_xplay_route"] == sorted(sigs) and not set(sigs) & set(_capi.EXPORTS)
-    for fn, params in decls:
-        want = [ctypes.c_void_p if "*" in p else (ctypes.c_int64 if "int64_t" in p else ctypes.c_int) for p in params.split(",")]
-        assert sigs[fn] == want
-    assert sigs["brl_xplay_route"] == _capi.league_signatures()["brl_league_route"]      # the same call, another grouping
+    sigs = _capi.SIGNATURES      # (every header against its entry: tests/test_capi_cpu.py)
+    assert sigs["brl_crossplay.h"]["brl_xplay_route"] == sigs["brl_league.h"]["brl_league_route"]      # the same call, another grouping
 
 
 LINEUP_CASES = {

@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from brl_amd import _capi, lines
+from brl_amd import lines
 from tests import board_records_ref as R
 from tests import lines_ref as F
 
@@ -29,12 +29,6 @@ def _rows(row):
 # ---- the header and the binding -------------------------------------------------------------------------------------------------
 def test_the_header_states_what_the_binding_and_the_host_read():
     text = open(os.path.join(ROOT, "include", "brl_lines.h")).read()
-    names = sorted(set(re.findall(r"\bint (brl_lines_\w+)\(", text)))
-    assert names == sorted(_capi.lines_argtypes()) == ["brl_lines_expand", "brl_lines_finish", "brl_lines_imp", "brl_lines_init"]
-    assert not set(_capi.lines_argtypes()) & set(_capi.EXPORTS)
-    for name, args in _capi.lines_argtypes().items():        # one argtype per parameter of the prototype
-        proto = re.search(r"\bint " + name + r"\((.*?)\);", text, re.S).group(1)
-        assert len(args) == proto.count(",") + 1, name
     for macro, value in (("BRL_LINES_MAX_K", lines.MAX_K), ("BRL_LINES_MAX_CALLS", lines.MAX_CALLS), ("BRL_LINE_EMPTY", lines.EMPTY),
                          ("BRL_LINE_FINISHED", lines.FINISHED), ("BRL_LINE_VOID", lines.VOID), ("BRL_LINE_GREEDY", lines.GREEDY)):
         assert re.search(r"#define " + macro + r" " + str(value) + r"\b", text), macro

@@ -100,9 +100,6 @@ def test_the_header_states_the_layout_the_host_reads():
     order = [text.index(f" {name};") for name in par.PAR_DTYPE.names]
     assert order == sorted(order)
     assert [par.PAR_DTYPE.fields[n][1] for n in par.PAR_DTYPE.names] == [0, 4, 8, 12, 16, 24]
-    from brl_amd import _capi
-    assert sorted(_capi.par_argtypes()) == ["brl_par", "brl_par_imp"]
-    assert not set(_capi.par_argtypes()) & set(_capi.EXPORTS)
 
 
 def test_the_host_imp_scale_is_the_reference_scale():
